@@ -28,6 +28,9 @@ policies / 10k rules with CEL conditions).
 Multi-GPU: independent request shards per rank (weak scaling), no data-path collective; the only collective is the
 one-time RCCL broadcast of the lowered policy image from rank 0.  `--inproc-gpus M` adds a single-process leg: one
 engine over M devices, cbh_check_batch sharding each batch into contiguous request ranges behind the C ABI.
+
+`--dump-outputs DIR` writes, after the timed region, a fixed seeded sample of the decisions its last sweep left on the device
+(see dump_outputs) as DIR/<name>.npy: the inputs are seeded, so two builds run with the same arguments compare array for array.
 """
 from __future__ import annotations
 
@@ -68,6 +71,43 @@ def pmc_traffic(kernel, workload):
     return None, None
 
 
+DUMP_TUPLES = 1 << 20                   # --dump-outputs: sampled (batch, tuple) pairs of the last timed step
+DUMP_REQUESTS = 1 << 18                 # ... and sampled (batch, request) pairs
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, table, dbatches):
+    """--dump-outputs: what the last timed sweep left in the batches' device results, as a caller of the resident path receives
+    them (cbh_result_download, input order), for a fixed seeded sample spread over every batch of the sweep.  Per sampled tuple:
+    effect and status (float32), policy and scope (float64: exact for uint32); per sampled request: the effective-derived-role
+    mask as two 32-bit halves (float64, exact); `batch`, `tuple` and `request` name the samples.  ~48 MB in all."""
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(0)
+    n_b = len(dbatches)
+    cols = {k: [] for k in ("batch", "tuple", "effect", "status", "policy", "scope", "request_batch", "request", "edr_lo", "edr_hi")}
+    for b, db in enumerate(dbatches):
+        res = table.download(db)
+        kt = max(1, min(res.effect.size, DUMP_TUPLES // n_b))
+        ti = np.sort(rng.choice(res.effect.size, kt, replace=False))
+        cols["batch"].append(np.full(kt, b, np.float64))
+        cols["tuple"].append(ti.astype(np.float64))
+        for name, dt in (("effect", np.float32), ("status", np.float32), ("policy", np.float64), ("scope", np.float64)):
+            cols[name].append(getattr(res, name)[ti].astype(dt))
+        kr = max(1, min(res.edr.size, DUMP_REQUESTS // n_b))
+        ri = np.sort(rng.choice(res.edr.size, kr, replace=False))
+        edr = res.edr[ri]
+        cols["request_batch"].append(np.full(kr, b, np.float64))
+        cols["request"].append(ri.astype(np.float64))
+        cols["edr_lo"].append((edr & np.uint64(0xFFFFFFFF)).astype(np.float64))
+        cols["edr_hi"].append((edr >> np.uint64(32)).astype(np.float64))
+    arrays = {k: np.concatenate(v) for k, v in cols.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, "output dump of %d bytes exceeds %d" % (total, DUMP_MAX_BYTES)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return total
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -91,7 +131,11 @@ def main():
     ap.add_argument("--check-first", action="store_true",
                     help="measurement aid (A/B runs): with --no-cpu-baseline, still compare every tuple of the first batch with oracle/ccheck.cpp after the timed region")
     ap.add_argument("--inproc-gpus", type=int, default=0, help="also time one engine over this many devices in THIS process")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a fixed seeded sample of what the last step computed as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # stdout carries exactly one JSON line.  RCCL writes its banner and its warnings to file descriptor 1 from its own threads
     # (seen: a warning landing in the middle of the line), so everything else that writes there is sent to stderr and the
@@ -230,6 +274,10 @@ def main():
     if use_dist:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
+
+    dumped = None
+    if rank == 0 and args.dump_outputs:   # (outside the timed region: the results of its last sweep, before any side leg launches)
+        dumped = {"dir": args.dump_outputs, "bytes": dump_outputs(args.dump_outputs, table, dbatches)}
 
     res = table.download(dbatches[0])
     eff = res.effect
@@ -629,6 +677,7 @@ def main():
             "target_T": target_t,
             "resolve_kernel_ms": resolve_ms,
             "allow_fraction": float((eff == 1).mean()),
+            "outputs_dumped": dumped,
             "policy_bcast_ms": bcast_ms,
             "policy_bcast_note": dist_note or ("RCCL broadcast of the %d-byte image from rank 0 (world %d) + cbh_table_adopt_device_image" % (len(lt.blob), world) if use_dist else "skipped (CBH_BENCH_NO_DIST=1)"),
         }
