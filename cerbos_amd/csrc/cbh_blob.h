@@ -369,7 +369,8 @@ enum CbhOp {
   OP_SIZE = 31, OP_STARTSWITH = 32, OP_ENDSWITH = 33, OP_CONTAINS = 34,
   OP_TIMESTAMP = 35, OP_DURATION = 36, OP_TIMESINCE = 37, OP_NOW = 38,
   OP_EDRHAS = 39,    // push (derived role bit arg) in runtime.effectiveDerivedRoles
-  OP_LOCAL = 40,     // push local arg
+  OP_LOCAL = 40,     // push local arg; cel.bind(v, init, body): arg 0x100 | slot stores TOS (init, kept) into local slot, arg 0x200
+                     // ends the bind - pop body; TOS = init if that is an error, else body
   OP_ITER_BEGIN = 41, // pop container -> iteration slot arg ; next word = kind | (end_pc << 8)
   OP_ITER_NEXT = 42,  // arg = slot; next word = end_pc : exhausted -> pc = end_pc, else bind locals
   OP_ITER_ACC = 43,   // arg = slot; next word = loop_pc : pop predicate, fold, maybe finish
@@ -398,7 +399,11 @@ enum CbhOp {
   OP_STRCAT = 66,     // pop b, a (strings or ropes) -> the rope a ++ b: its parts side by side in the lane's arena, no byte is copied
   OP_STRCASE = 67,    // arg 1 lowerAscii / 2 upperAscii: TOS string -> the rope that reads it through the case mapping
   OP_LISTFN = 65,     // arg 0 reverse: TOS list -> reversed copy in the arena; 1 slice: pop end, start; TOS list -> the view
-                      // [start, end) of it; 2 lists.range: TOS int n -> [0 .. n) in the arena
+                      // [start, end) of it; 2 lists.range: TOS int n -> [0 .. n) in the arena.  arg >= 0x100: cel-go extension functions on
+                      // values the request supplies - ext.Math and s.split(sep[, n]): arg = function (CbhExtFn) | argument count << 8;
+                      // pops the arguments, pushes the result (cbh_vm.h ext_op).  split's result is the list of the pieces in the lane's
+                      // arena, each a rope of one window of s.  (Inside this label, not one of its own: a case label more costs the
+                      // interpreter its second wave, cbh_interp.h)
   OP_IPFN = 68,       // cel-go ext.Network on a string the request supplies.  arg 0 isIP(s), 8 / 9 isIP(s, 4 / 6), 7 ip.isCanonical(s); 1 ip(s).family(),
                       // 2 isUnspecified, 3 isLoopback, 4 isLinkLocalUnicast, 5 isLinkLocalMulticast, 6 isGlobalUnicast (an error where
                       // ip(s) fails); 10: pop ip, cidr (strings) -> cidr(c).containsIP(ip)
@@ -412,6 +417,10 @@ enum CbhOp {
                       // emitted only where it is the WHOLE expression of an output's part or of a variable: nothing else ever sees the tag
   OP_NOPS
 };
+enum CbhExtFn { MF_ABS = 0, MF_SIGN = 1, MF_CEIL = 2, MF_FLOOR = 3, MF_ROUND = 4, MF_TRUNC = 5, MF_SQRT = 6, MF_ISNAN = 7, MF_ISINF = 8,
+                MF_ISFINITE = 9, MF_BITNOT = 10, MF_BITAND = 11, MF_BITOR = 12, MF_BITXOR = 13, MF_SHL = 14, MF_SHR = 15,
+                MF_GREATEST = 16, MF_LEAST = 17,   // greatest / least: one list argument, or 1 .. N numbers
+                XF_SPLIT = 18 };                   // s.split(sep) (2 arguments) / s.split(sep, n) (3)
 enum CbhIterKind { IT_ALL = 0, IT_EXISTS = 1, IT_EXISTS_ONE = 2, IT_FILTER = 3, IT_MAP = 4,   // filter / map build a list in the lane's arena
                    IT_MAP_FILTER = 5 };   // map(x, pred, expr) / transformList(i, v, pred, expr): the body leaves pred and expr
 #define CBH_ARENA_ENTRIES 48u   /* values per lane a program may build lists from; more marks the tuple CBH_ST_UNSUPPORTED */

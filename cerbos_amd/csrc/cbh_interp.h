@@ -170,9 +170,11 @@ __device__ __forceinline__ u32 run_uniform_impl(const KernelArgs* ka, const VmLd
       }
       case OP_EQ: case OP_NE: case OP_LT: case OP_LE: case OP_GT: case OP_GE: case OP_IN: {
         Val y = TOPV(0), x = TOPV(1); --sp;
-        if (x.t == CBH_T_ROPE || y.t == CBH_T_ROPE) {   // ropes are compared by content, out of line (cbh_vm.h rope_op)
+        // ropes are compared by content, out of line (cbh_vm.h rope_op) - so is a string's membership in an arena list, which may
+        // hold ropes (split)
+        if (x.t == CBH_T_ROPE || y.t == CBH_T_ROPE || (op == OP_IN && x.t == CBH_T_STRING && local_list(y))) {
           if (x.t == CBH_T_ERR || y.t == CBH_T_ERR) { FAILTOP2(x, y, 0); break; }
-          if (op == OP_EQ || op == OP_NE || (op == OP_IN && x.t == CBH_T_ROPE)) {
+          if (op == OP_EQ || op == OP_NE || (op == OP_IN && is_strlike(x.t))) {
             const SlowVal r = rope_op(ka, lds, op == OP_EQ ? ROPE_EQ : op == OP_NE ? ROPE_NE : ROPE_IN, x, y);
             SETTOP(mk(r.t, r.v));
           } else {   // an ordering of ropes, or membership IN a rope: left to the caller's engine / no such overload
@@ -515,7 +517,15 @@ __device__ __forceinline__ u32 run_uniform_impl(const KernelArgs* ka, const VmLd
         else PUSHV(mk_bool(!(a >> 31) && L.edr == c.t.const_val[a & 0x7FFFFFFFu]));
         break;
       }
-      case OP_LOCAL: PUSHV(mk(c.l_tag[a * CBH_BLOCK + c.tid], c.l_val[a * CBH_BLOCK + c.tid])); break;
+      case OP_LOCAL: {
+        if (a >> 8) {   // cel.bind: 0x100 | slot stores TOS (init) into the slot; 0x200 pops the body - an erring init is the result
+          if (a & 0x100u) { c.l_tag[(a & 0xFFu) * CBH_BLOCK + c.tid] = ST(sp - 1); c.l_val[(a & 0xFFu) * CBH_BLOCK + c.tid] = SV(sp - 1); }
+          else { const Val body = TOPV(0); --sp; if (ST(sp - 1) != CBH_T_ERR) SETTOP(body); }
+          break;
+        }
+        PUSHV(mk(c.l_tag[a * CBH_BLOCK + c.tid], c.l_val[a * CBH_BLOCK + c.tid]));
+        break;
+      }
       // ---- comprehensions: wave-uniform loop, per-lane progress
       case OP_ITER_BEGIN: {   // a = slot; next word = kind
         Val x = TOPV(0); --sp;
@@ -585,7 +595,7 @@ __device__ __forceinline__ u32 run_uniform_impl(const KernelArgs* ka, const VmLd
           // of a turn the predicate lets through
           const bool is_map = (st & 0xFF) != IT_FILTER;
           const bool bad_guard = guard.t != CBH_T_BOOL, skipped = !bad_guard && !guard.v;
-          if (!bad_guard && !skipped && is_map && x.t == CBH_T_ROPE) {   // a rope never becomes a list element (cbh_vm.h)
+          if (!bad_guard && !skipped && is_map && x.t == CBH_T_ROPE) {   // a rope becomes a list element only through split (cbh_vm.h)
             if (live) L.status |= CBH_ST_UNSUPPORTED;
             if (TRACE) { IT_ERR_LO(a) = 0; IT_ERR_HI(a) = 0; }
             st |= ITS_FAIL; st &= ~ITS_RUNNING;
@@ -750,6 +760,14 @@ __device__ __forceinline__ u32 run_uniform_impl(const KernelArgs* ka, const VmLd
         break;
       }
       case OP_LISTFN: {
+        if (a >> 8) {   // a = CbhExtFn | argument count << 8: ext.Math / split on request values (cbh_vm.h ext_op reads the stack)
+          const SlowVal r = ext_op(ka, lds, a, sp, ap);
+          sp -= (int)(a >> 8) - 1;
+          ap = r.status >> 16;
+          if (live) L.status |= r.status & 0xFFFFu;
+          SETTOP(mk(r.t, r.v));
+          break;
+        }
         if (a == 1) {   // slice(start, end): a view of the same elements
           Val e = TOPV(0), b0 = TOPV(1), x = TOPV(2); sp -= 2;
           if (x.t != CBH_T_LIST || b0.t != CBH_T_INT || e.t != CBH_T_INT) { if (x.t == CBH_T_ERR) break; FAILTOP2(b0, e, CBH_ERR_NO_SUCH_OVERLOAD); break; }

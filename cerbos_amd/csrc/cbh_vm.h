@@ -384,7 +384,10 @@ __device__ __forceinline__ Val heap_get(const Ctx& c, u32 sel, u32 idx) {
 // through the mapping) -; whoever needs its bytes walks the parts.  Only the operand-stack interpreter makes and reads ropes
 // (cbh_interp.h: equality, `in`, prefix / suffix / substring search, size(); anything else flags the tuple UNSUPPORTED), through
 // ONE out-of-line function (rope_op below), so that the shared comparison code and the kernels without an interpreter stay as they are.
-// A rope never becomes a list element.
+// A rope becomes a list element only as a piece of s.split(sep) (split_op below).  Such a list is read like any other - size, indexing,
+// comprehensions hand out the ropes - and `s in list` with a string or rope s goes through rope_op; anything else that compares its
+// elements (list equality, hasIntersection / isSubset, intersect / except, a non-string `in` it) meets the rope in val_equal,
+// which leaves the tuple to the caller's engine.
 __device__ __forceinline__ u32 rope_parts(u64 v) { return (u32)v & 0xFFFFu; }
 __device__ __forceinline__ Val mk_rope(u32 off, u32 parts) { return mk(CBH_T_ROPE, ((u64)CBH_HEAP_LOCAL << 62) | ((u64)off << 32) | parts); }
 __device__ __forceinline__ bool is_strlike(u32 t) { return t == CBH_T_STRING || t == CBH_T_ROPE; }
@@ -483,14 +486,15 @@ __device__ inline bool scalar_equal(const Ctx& c, Val a, Val b) {
 }
 
 __device__ inline bool val_equal(const Ctx& c, Lane& L, Val a, Val b) {
+  if (a.t == CBH_T_ROPE || b.t == CBH_T_ROPE) { L.status |= CBH_ST_UNSUPPORTED; return false; }   // a piece of split() in a list (cbh_interp.h)
   if (a.t == CBH_T_LIST && b.t == CBH_T_LIST) {
     u32 n = cont_len(a.v);
     if (n != cont_len(b.v)) return false;
     for (u32 i = 0; i < n; ++i) {
       Val x = heap_get(c, cont_sel(a.v), cont_off(a.v) + i);
       Val y = heap_get(c, cont_sel(b.v), cont_off(b.v) + i);
-      if (x.t == CBH_T_LIST || x.t == CBH_T_MAP || y.t == CBH_T_LIST || y.t == CBH_T_MAP) {
-        L.status |= CBH_ST_UNSUPPORTED;  // nested container equality is not on the device
+      if (x.t == CBH_T_LIST || x.t == CBH_T_MAP || y.t == CBH_T_LIST || y.t == CBH_T_MAP || x.t == CBH_T_ROPE || y.t == CBH_T_ROPE) {
+        L.status |= CBH_ST_UNSUPPORTED;  // nested container equality is not on the device (nor are the pieces of split() in a list)
         return false;
       }
       if (!scalar_equal(c, x, y)) return false;
@@ -941,6 +945,9 @@ __device__ SlowVal compare_op_slow(const KernelArgs* ka, u32 req, u32 op, Val x,
   return SlowVal{r.t, L.status, r.v};
 }
 
+// A list in the lane's arena: it may hold ropes (split_op)
+__device__ __forceinline__ bool local_list(Val v) { return v.t == CBH_T_LIST && cont_sel(v.v) == CBH_HEAP_LOCAL; }
+
 // Everything the interpreter does WITH a rope (cbh_interp.h), out of line and by value like compare_op_slow.
 //   kind 0 / 1  x == y / x != y          kind 2  x in y (list or map keys)      kind 3 / 4 / 5  startsWith / endsWith / contains
 //   kind 6      size(x) in code points
@@ -980,6 +987,168 @@ __device__ SlowVal rope_op(const KernelArgs* ka, const VmLds lds, u32 kind, Val 
     }
   }
   return SlowVal{CBH_T_BOOL, 0, (u64)hit};
+}
+
+// s.split(sep) / s.split(sep, limit): Go's strings.Split / SplitN as cel-go ext/strings.go calls them - an empty separator splits
+// into code points, limit 0 gives [], 1 gives [s], a negative limit splits everything.  The k pieces become a list in the lane's
+// arena from `ap`: the elements (ropes) at [ap, ap + k), each one's part - a window of s - at [ap + k, ap + 2k).  -> the list, an
+// error, or status CBH_ST_UNSUPPORTED (a rope operand, or pieces the arena cannot hold).
+__device__ inline SlowVal split_op(const Ctx& c, Val x, Val sep, Val lim, u32 ap) {
+  if (x.t == CBH_T_ERR) return SlowVal{x.t, 0, x.v};
+  if (sep.t == CBH_T_ERR) return SlowVal{sep.t, 0, sep.v};
+  if (lim.t == CBH_T_ERR) return SlowVal{lim.t, 0, lim.v};
+  if (x.t == CBH_T_ROPE || sep.t == CBH_T_ROPE) return SlowVal{CBH_T_ERR, CBH_ST_UNSUPPORTED, 0};
+  if (x.t != CBH_T_STRING || sep.t != CBH_T_STRING || lim.t != CBH_T_INT) return SlowVal{CBH_T_ERR, 0, (u64)CBH_ERR_NO_SUCH_OVERLOAD};
+  gbytes p, q; u32 n, m;
+  str_span(c, (u32)x.v, p, n); str_span(c, (u32)sep.v, q, m);
+  const i64 limit = (i64)lim.v;
+  const u64 list = ((u64)CBH_HEAP_LOCAL << 62) | ((u64)ap << 32);
+  if (limit == 0) return SlowVal{CBH_T_LIST, 0, list};
+  if (n > CBH_ROPE_WINDOW_MAX) return SlowVal{CBH_T_ERR, CBH_ST_UNSUPPORTED, 0};
+  u32 total = 0;
+  for (u32 pass = 0; pass < 2; ++pass) {   // pass 0 counts the pieces, pass 1 writes them
+    u32 k = 0, from = 0;
+    auto piece = [&](u32 first, u32 bytes) {
+      if (pass == 1) {
+        arena_put(c, ap + k, mk_rope(ap + total + k, 1));
+        arena_put(c, ap + total + k, mk(CBH_T_STRING, rope_window((u32)x.v, first, bytes)));
+      }
+      ++k;
+    };
+    if (limit != 1) {
+      u32 i = 0;
+      while (m == 0 ? i < n : i + m <= n) {
+        if (limit > 0 && (i64)k == limit - 1) break;   // the last piece is the rest
+        if (m == 0) {   // one code point
+          u32 j = i + 1;
+          while (j < n && (p[j] & 0xC0u) == 0x80u) ++j;
+          piece(i, j - i);
+          i = from = j;
+          continue;
+        }
+        u32 j = 0;
+        while (j < m && p[i + j] == q[j]) ++j;
+        if (j < m) { ++i; continue; }
+        piece(from, i - from);
+        i += m; from = i;
+      }
+    }
+    if (m != 0 || limit == 1 || from < n) piece(from, n - from);   // (exploded into code points, s leaves no empty rest)
+    if (pass == 0) {
+      total = k;
+      if (ap > CBH_ARENA_ENTRIES || 2u * total > CBH_ARENA_ENTRIES - ap) return SlowVal{CBH_T_ERR, CBH_ST_UNSUPPORTED, 0};
+    }
+  }
+  return SlowVal{CBH_T_LIST, 0, list | total};
+}
+
+// cel-go ext.Math on request values (CbhExtFn): function `fn` of the `n` arguments at [base, base + n) of the lane's operand stack.
+// int, uint and double each give their
+// own type; abs(INT64_MIN) overflows; ceil / floor / round / trunc and isNaN / isInf / isFinite take doubles only, NaN and the
+// infinities pass the rounding functions unchanged, round is Go's math.Round; bit operations take int x int or uint x uint, a shift
+// an int offset (negative: CBH_ERR_NEG_SHIFT; 64 and more: 0; the 64-bit pattern moves, so an int's right shift is logical).
+// greatest / least (one list, or 1 .. N numbers) compare across numeric types and give the winning element as it is, the first on
+// a tie; a NaN never wins against an element and an element never wins against a NaN (oracle/celeval.py _math_extreme).
+__device__ inline SlowVal math_op(const Ctx& c, u32 fn, u32 n, int base) {
+  const SlowVal bad{CBH_T_ERR, 0, (u64)CBH_ERR_NO_SUCH_OVERLOAD};
+  for (u32 k = 0; k < n; ++k)   // the first failing argument is the error cel-go reports
+    if (ST(base + (int)k) == CBH_T_ERR) return SlowVal{CBH_T_ERR, 0, SV(base + (int)k)};
+  const Val x = mk(ST(base), SV(base));
+  if (fn == MF_GREATEST || fn == MF_LEAST) {
+    const bool from_list = n == 1 && x.t == CBH_T_LIST;
+    const u32 cnt = from_list ? cont_len(x.v) : n;
+    if (cnt == 0) return bad;
+    Val best = from_list ? heap_get(c, cont_sel(x.v), cont_off(x.v)) : x;
+    if (!is_num(best.t)) return bad;
+    for (u32 k = 1; k < cnt; ++k) {
+      const Val e = from_list ? heap_get(c, cont_sel(x.v), cont_off(x.v) + k) : mk(ST(base + (int)k), SV(base + (int)k));
+      if (!is_num(e.t)) return bad;
+      const int r = num_cmp(e, best);
+      if (r != 2 && (fn == MF_GREATEST ? r > 0 : r < 0)) best = e;
+    }
+    return SlowVal{best.t, 0, best.v};
+  }
+  if (n == 1) {
+    const double d = as_f64(x.v);
+    switch (fn) {
+      case MF_ABS:
+        if (x.t == CBH_T_UINT) return SlowVal{x.t, 0, x.v};
+        if (x.t == CBH_T_INT) {
+          if ((i64)x.v == INT64_MIN) return SlowVal{CBH_T_ERR, 0, (u64)CBH_ERR_INT_OVERFLOW};
+          return SlowVal{x.t, 0, (u64)((i64)x.v < 0 ? -(i64)x.v : (i64)x.v)};
+        }
+        if (x.t == CBH_T_DOUBLE) return SlowVal{x.t, 0, f64_bits(fabs(d))};
+        return bad;
+      case MF_SIGN:
+        if (x.t == CBH_T_UINT) return SlowVal{x.t, 0, (u64)(x.v != 0)};
+        if (x.t == CBH_T_INT) return SlowVal{x.t, 0, (u64)(i64)(((i64)x.v > 0) - ((i64)x.v < 0))};
+        if (x.t == CBH_T_DOUBLE) return SlowVal{x.t, 0, d != d ? x.v : f64_bits(d > 0 ? 1.0 : d < 0 ? -1.0 : 0.0)};
+        return bad;
+      case MF_SQRT: {
+        if (!is_num(x.t)) return bad;
+        const double v = x.t == CBH_T_DOUBLE ? d : x.t == CBH_T_INT ? (double)(i64)x.v : (double)x.v;
+        return SlowVal{CBH_T_DOUBLE, 0, f64_bits(sqrt(v))};   // (NaN below zero)
+      }
+      case MF_BITNOT:
+        if (x.t == CBH_T_UINT || x.t == CBH_T_INT) return SlowVal{x.t, 0, ~x.v};
+        return bad;
+      default: break;
+    }
+    if (x.t != CBH_T_DOUBLE || fn < MF_CEIL || fn > MF_ISFINITE) return bad;
+    const bool nan = d != d, inf = !nan && (d - d) != 0.0;
+    if (fn == MF_ISNAN) return SlowVal{CBH_T_BOOL, 0, (u64)nan};
+    if (fn == MF_ISINF) return SlowVal{CBH_T_BOOL, 0, (u64)inf};
+    if (fn == MF_ISFINITE) return SlowVal{CBH_T_BOOL, 0, (u64)(!nan && !inf)};
+    if (nan || inf) return SlowVal{x.t, 0, x.v};
+    double r;
+    if (fn == MF_CEIL) r = ceil(d);
+    else if (fn == MF_FLOOR) r = floor(d);
+    else {
+      r = trunc(d);
+      if (fn == MF_ROUND && fabs(d - r) >= 0.5) r += d < 0 ? -1.0 : 1.0;   // Go's math.Round: half away from zero, exact
+      r = copysign(r, d);
+    }
+    return SlowVal{CBH_T_DOUBLE, 0, f64_bits(r)};
+  }
+  if (n != 2) return bad;
+  const Val y = mk(ST(base + 1), SV(base + 1));
+  if (fn == MF_BITAND || fn == MF_BITOR || fn == MF_BITXOR) {
+    if (!((x.t == CBH_T_INT && y.t == CBH_T_INT) || (x.t == CBH_T_UINT && y.t == CBH_T_UINT))) return bad;
+    return SlowVal{x.t, 0, fn == MF_BITAND ? (x.v & y.v) : fn == MF_BITOR ? (x.v | y.v) : (x.v ^ y.v)};
+  }
+  if (fn == MF_SHL || fn == MF_SHR) {
+    if ((x.t != CBH_T_INT && x.t != CBH_T_UINT) || y.t != CBH_T_INT) return bad;
+    const i64 off = (i64)y.v;
+    if (off < 0) {
+      const u64 mag = (u64)0 - y.v;   // the detail holds magnitudes below 2^55; a larger one stays unnamed (CBH_ERR_OTHER)
+      if (mag >> 55) return SlowVal{CBH_T_ERR, 0, (u64)CBH_ERR_OTHER};
+      return SlowVal{CBH_T_ERR, 0, (u64)CBH_ERR_NEG_SHIFT | (((mag << 1) | (fn == MF_SHR ? 1u : 0u)) << 8)};
+    }
+    if (off >= 64) return SlowVal{x.t, 0, 0};
+    return SlowVal{x.t, 0, fn == MF_SHL ? x.v << off : x.v >> off};
+  }
+  return bad;
+}
+
+// The extension functions on request values (cbh_blob.h OP_LISTFN, arg >= 0x100), out of line and by value like rope_op: `a` = function (CbhExtFn)
+// | argument count << 8; the arguments are the top `a >> 8` entries of the lane's operand stack (`sp` = its depth), the first one
+// deepest; `ap` = the fill of the lane's arena.  -> the result, the CBH_ST_* bits to raise in status bits 0..15 and the arena's new
+// fill in bits 16..
+#ifndef CBH_HOSTSIM
+__attribute__((noinline))
+#endif
+__device__ SlowVal ext_op(const KernelArgs* ka, const VmLds lds, u32 a, int sp, u32 ap) {
+  const Ctx c = ctx_from_memory(ka, lds);
+  const u32 fn = a & 0xFFu, n = a >> 8;
+  if (n == 0 || (int)n > sp) return SlowVal{CBH_T_ERR, ap << 16, (u64)CBH_ERR_NO_SUCH_OVERLOAD};
+  const int base = sp - (int)n;
+  if (fn != XF_SPLIT) { SlowVal r = math_op(c, fn, n, base); r.status = ap << 16; return r; }
+  const Val x = mk(ST(base), SV(base)), sep = n > 1 ? mk(ST(base + 1), SV(base + 1)) : mk_err(),
+            lim = n > 2 ? mk(ST(base + 2), SV(base + 2)) : mk(CBH_T_INT, ~0ull);
+  SlowVal r = split_op(c, x, sep, lim, ap);
+  if (r.t == CBH_T_LIST) ap = cont_off(r.v) + 2u * cont_len(r.v);
+  r.status |= ap << 16;
+  return r;
 }
 
 // Same-type fast paths of compare_op for the inline fused-leaf evaluation.

@@ -86,6 +86,15 @@ _ID_ONLY_OPS = frozenset([OP_RET, OP_CONST, OP_COL, OP_HASCOL, OP_REQSTR, OP_ROL
                           OP_IN, OP_NOT, OP_JF, OP_JT, OP_AND, OP_OR, OP_JTERN, OP_JMP, OP_POP, OP_LEAF, OP_EDRHAS, OP_LOCAL,
                           OP_ITER_BEGIN, OP_ITER_NEXT, OP_ITER_ACC, OP_ITER_END, OP_HASINTERSECTION, OP_ISSUBSET, OP_LEAF_BIN,
                           OP_TERN, OP_TREE_BEGIN, OP_TREE_ACC, OP_TREE_END, OP_UNSUPPORTED, OP_TS_GETTER, OP_VARSCOPE, OP_OUT, OP_LISTOP, OP_LISTFN, OP_EDREQ, OP_EDRVAL])
+# (OP_LISTFN's ext.Math functions read no string bytes; its split does, and its lowering says so itself)
+
+# cel-go ext.Math functions on request values, OP_LISTFN with arg = function | argument count << 8 (cbh_blob.h CbhExtFn):
+# name -> (function, argument count; None = 1 .. N)
+_MATH_FNS = {"abs": (0, 1), "sign": (1, 1), "ceil": (2, 1), "floor": (3, 1), "round": (4, 1), "trunc": (5, 1), "sqrt": (6, 1),
+             "isNaN": (7, 1), "isInf": (8, 1), "isFinite": (9, 1), "bitNot": (10, 1), "bitAnd": (11, 2), "bitOr": (12, 2),
+             "bitXor": (13, 2), "bitShiftLeft": (14, 2), "bitShiftRight": (15, 2), "greatest": (16, None), "least": (17, None)}
+XF_SPLIT = 18
+LOCAL_BIND_STORE, LOCAL_BIND_END = 0x100, 0x200   # OP_LOCAL's cel.bind forms
 
 
 class LoweringError(ValueError):
@@ -752,6 +761,7 @@ def _builds_list(ast):
         return ast[1] in ("filter", "map", "transformList")
     if k == "call":
         return ast[1] in ("intersect", "except", "slice") or (ast[1] == "reverse" and ast[2] is not None and _builds_list(ast[2])) \
+            or (ast[1] == "split" and ast[2] is not None and len(ast[3]) in (1, 2)) \
             or (ast[1] == "range" and ast[2] is not None and ast[2][0] == "ident" and ast[2][1] == "lists")
     if k == "bin" and ast[1] == "+":
         return _builds_list(ast[2]) or _builds_list(ast[3])
@@ -1152,7 +1162,26 @@ class _FuncCompiler:
         if k == "varscope":   # trace programs: the inlined definition of variable ast[1]
             self._expr(ast[2])
             return self.emit(OP_VARSCOPE, pb.tid(ast[1]) | (ast[3] << 23))
+        if k == "bind":
+            return self._bind(ast)
         return self.unsupported("%s expression" % k)
+
+    def _bind(self, ast):
+        """cel.bind(v, init, body) whose init reads the request (a constant one was substituted by the folding): init is evaluated
+        once and stored in a local slot - the slots comprehension variables use, CBH_MAX_LOCALS of them - that `v` reads in the body.
+        An erring init is the result whatever the body does (oracle/celeval.py evaluates it first)."""
+        _, var, init, body = ast
+        slot = len(self.locals)
+        if var in self.locals or sorted(self.locals.values()) != list(range(slot)) or slot >= MAX_LOCALS:
+            return self.unsupported("cel.bind beyond the device's local slots")
+        self._expr(init)
+        self.emit(OP_LOCAL, LOCAL_BIND_STORE | slot)
+        saved = dict(self.locals)
+        self.locals[var] = slot
+        self.max_locals = max(self.max_locals, len(self.locals))
+        self._expr(body)
+        self.locals = saved
+        return self.emit(OP_LOCAL, LOCAL_BIND_END, -1)
 
     def _call(self, ast):
         _, name, target, args = ast
@@ -1317,6 +1346,20 @@ class _FuncCompiler:
                 return self.emit(OP_LISTOP, 0 if name == "intersect" else 1, -1)
             if name in ("isSubset", "is_subset") and n == 2:
                 return binary(OP_ISSUBSET)
+            if name == "split" and target is not None and n in (2, 3):
+                # Go's strings.Split / SplitN (cel-go ext/strings.go): the pieces as a list in the lane's arena, each a rope of one
+                # window of the string (cbh_vm.h split_op)
+                self.pb.needs_arena = True
+                self.pb.reads_string_bytes = True
+                for x in allargs:
+                    self._expr(x)
+                return self.emit(OP_LISTFN, XF_SPLIT | (n << 8), 1 - n)
+        elif target[1] == "math" and name in _MATH_FNS and args and len(args) == (_MATH_FNS[name][1] or len(args)) \
+                and self.depth + len(args) <= MAX_STACK:   # cel-go ext.Math (cbh_vm.h math_op); more arguments than the stack holds: flagged
+            fn = _MATH_FNS[name][0]
+            for x in args:
+                self._expr(x)
+            return self.emit(OP_LISTFN, fn | (len(args) << 8), 1 - len(args))
         elif target[1] == "lists" and name == "range" and n == 2:   # lists.range(n) = [0 .. n)
             self.pb.needs_arena = True
             self._expr(args[0])

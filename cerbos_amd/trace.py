@@ -24,7 +24,7 @@ class _LocalList:
         self.n = n
 TR_DRFAIL = 32   # cbh_check_wave.h CBH_TR_DRFAIL
 (ERR_OTHER, ERR_NO_SUCH_KEY, ERR_ATTR_MISSING, ERR_NO_SUCH_OVERLOAD, ERR_UNDEFINED_FIELD, ERR_DIV_BY_ZERO, ERR_MOD_BY_ZERO,
- ERR_INT_OVERFLOW, ERR_UINT_OVERFLOW, ERR_EDR_FAILED) = range(10)
+ ERR_INT_OVERFLOW, ERR_UINT_OVERFLOW, ERR_EDR_FAILED, ERR_NEG_SHIFT) = range(11)
 T_NULL, T_BOOL, T_INT, T_UINT, T_DOUBLE, T_STRING, T_LIST, T_MAP, T_TIMESTAMP, T_DURATION = range(10)
 T_EDRSET = 11   # include/cerbos_hip.h CBH_T_EDRSET
 HEAP_TABLE, HEAP_ROLES = 0, 2
@@ -69,6 +69,8 @@ class TraceDecoder:
                 sorted(n for i, n in enumerate(self.lt.dr_names) if (detail >> i) & 1))
         if code in _FIXED:
             return _FIXED[code]
+        if code == ERR_NEG_SHIFT:   # cel-go ext/math.go: detail bit 0 = bitShiftRight, the rest the offset's magnitude
+            return "math.bitShift%s() negative offset: -%d" % ("Right" if detail & 1 else "Left", detail >> 1)
         if code == ERR_NO_SUCH_KEY:
             return "no such key: %s" % self.string(detail)
         if code == ERR_UNDEFINED_FIELD:

@@ -431,6 +431,8 @@ int cbh_wire_check_requests_trail_pb(cbh_table* t, uint32_t device_index, const 
 #define CBH_ERR_UINT_OVERFLOW 8u    /* "unsigned integer overflow" */
 #define CBH_ERR_EDR_FAILED 9u       /* strict mode: "failed to compute effective derived roles [a, b]"; the 56-bit detail (w4, w5 = */
                                     /* the whole payload, code in the low byte) = mask of the failed roles, bit = edr_mask bit       */
+#define CBH_ERR_NEG_SHIFT 10u       /* "math.bitShiftLeft() negative offset: -<n>"; detail bit 0 = bitShiftRight, bits 1.. = n (the */
+                                    /* offset's magnitude, below 2^55)                                                              */
 #define CBH_TRACE_RECORD_WORDS 8u
 
 typedef struct cbh_trace {
