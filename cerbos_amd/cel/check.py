@@ -58,11 +58,14 @@ def _visit(n, bound, out):   # noqa: C901
         if n[1] not in bound and n[1] not in DECLARED and n[1] not in _TYPES:
             out.append("undeclared reference to '%s' (in container '')" % n[1])
         return
-    if k in ("select", "has"):
+    if k in ("select", "has", "optsel"):
         _visit(n[1], bound, out)
         msg = _message_type(n[1], bound)
         if isinstance(msg, dict) and n[2] not in msg:
             out.append("undefined field '%s'" % n[2])
+    elif k == "optindex" or k == "optelem":
+        for x in n[1:]:
+            _visit(x, bound, out)
     elif k == "index":
         _visit(n[1], bound, out)
         _visit(n[2], bound, out)

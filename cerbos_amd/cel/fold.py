@@ -147,7 +147,9 @@ def equal(a, b):
                 return False
         return True
     if isinstance(a, Opt):
-        return isinstance(b, Opt) and a.present == b.present and (not a.present or equal(a.value, b.value))
+        if not isinstance(b, Opt):   # cel-go's checker refuses optional(T) == T: nothing to pin
+            raise NotConst("optional compared with a value")
+        return a.present == b.present and (not a.present or equal(a.value, b.value))
     if isinstance(a, IPAddr):
         return isinstance(b, IPAddr) and a.a == b.a
     if isinstance(a, CIDR):
@@ -505,13 +507,30 @@ class _Eval:
                 return env[n[1]]
             raise NotConst(n[1])
         if k == "list":
-            return [self.ev(e, env) for e in n[1]]
+            out = []
+            for e in n[1]:
+                if e[0] == "optelem":   # [?o]: the element when o has a value
+                    o = self.ev(e[1], env)
+                    if not isinstance(o, Opt):
+                        raise NotConst("optional element")
+                    if o.present:
+                        out.append(o.value)
+                else:
+                    out.append(self.ev(e, env))
+            return out
         if k == "map":
             pairs = []
             for ke, ve in n[1]:
                 kk = self.ev(ke, env)
                 if not isinstance(kk, (bool, str)) and not (_is_num(kk) and not isinstance(kk, float)):
                     raise FoldError("unsupported key type")
+                if ve[0] == "optelem":   # {?k: o}: the entry when o has a value
+                    o = self.ev(ve[1], env)
+                    if not isinstance(o, Opt):
+                        raise NotConst("optional entry")
+                    if o.present:
+                        pairs.append((kk, o.value))
+                    continue
                 pairs.append((kk, self.ev(ve, env)))
             return _mkmap(pairs)
         if k == "not":
@@ -533,10 +552,23 @@ class _Eval:
             return self.ev(n[2] if c else n[3], env)
         if k == "bin":
             return self.binop(n[1], self.ev(n[2], env), self.ev(n[3], env))
-        if k == "index":
-            return self.index(self.ev(n[1], env), self.ev(n[2], env))
-        if k == "select":
+        if k in ("optsel", "optindex", "select", "index"):
             v = self.ev(n[1], env)
+            if k in ("optsel", "optindex") or isinstance(v, Opt):
+                # cel-go interpreter/attributes.go: from the first optional qualifier on, a qualifier only tests for presence
+                if isinstance(v, Opt):
+                    if not v.present:
+                        return v
+                    v = v.value
+                key = n[2] if k in ("optsel", "select") else self.ev(n[2], env)
+                if isinstance(v, dict) and (isinstance(key, str) or k in ("optindex", "index")):
+                    found, out = _map_get(v, key)
+                    return Opt(True, out) if found else Opt(False)
+                if isinstance(v, list) and k in ("optindex", "index") and _is_int(key):
+                    return Opt(True, v[key]) if 0 <= key < len(v) else Opt(False)
+                raise NotConst("optional qualifier")   # (another operand: not pinned)
+            if k == "index":
+                return self.index(v, self.ev(n[2], env))
             if isinstance(v, dict):
                 found, out = _map_get(v, n[2])
                 if not found:
@@ -718,6 +750,8 @@ class _Eval:
                 return Opt(True, vals[0])
             if name == "none" and nv == 0:
                 return Opt(False)
+            if name == "ofNonZeroValue" and nv == 1:
+                return Opt(not _is_zero(vals[0]), vals[0])
         if ns == "lists" and name == "range" and nv == 1:
             return [i for i in range(max(0, _need(vals[0], int)))]
         if ns == "sets" and nv == 2 and all(isinstance(v, list) for v in vals):
@@ -1080,7 +1114,18 @@ class _Eval:
                 return o.value
             if name == "orValue" and nv == 2:
                 return o.value if o.present else vals[1]
+            if name == "or" and nv == 2 and isinstance(vals[1], Opt):
+                return o if o.present else vals[1]
         raise NotConst("function %s/%d" % (name, nv))
+
+
+def _is_zero(v):
+    """cel-go traits.Zeroer (optional.ofNonZeroValue): null, false, 0, 0u, 0.0, "", b"", [] and {}; other types are not pinned."""
+    if v is None:
+        return True
+    if isinstance(v, (bool, int, float, str, bytes, list, dict)):
+        return not v
+    raise NotConst("ofNonZeroValue")
 
 
 _HIER = {"ancestorOf": _h_ancestor, "descendentOf": lambda h, o: _h_ancestor(o, h), "immediateParentOf": _h_imm_parent,
@@ -1182,7 +1227,8 @@ def to_ast(v):
     return None
 
 
-_FOLDABLE = ("list", "map", "not", "neg", "and", "or", "tern", "bin", "index", "select", "has", "bind", "comp", "call")
+_FOLDABLE = ("list", "map", "not", "neg", "and", "or", "tern", "bin", "index", "select", "has", "bind", "comp", "call",
+             "optsel", "optindex", "optelem")
 
 
 def _const_node(n):
@@ -1198,9 +1244,9 @@ def _const_node(n):
 
 def _children(n):
     k = n[0]
-    if k in ("select", "has", "not", "neg"):
+    if k in ("select", "has", "not", "neg", "optsel", "optelem"):
         return [n[1]]
-    if k == "index":
+    if k in ("index", "optindex"):
         return [n[1], n[2]]
     if k == "call":
         return ([n[2]] if n[2] is not None else []) + list(n[3])
@@ -1224,11 +1270,11 @@ def _children(n):
 def _rebuild(n, ch):
     k = n[0]
     it = iter(ch)
-    if k in ("select", "has"):
+    if k in ("select", "has", "optsel"):
         return (k, next(it), n[2])
-    if k in ("not", "neg"):
+    if k in ("not", "neg", "optelem"):
         return (k, next(it))
-    if k == "index":
+    if k in ("index", "optindex"):
         return (k, next(it), next(it))
     if k == "call":
         tgt = next(it) if n[2] is not None else None

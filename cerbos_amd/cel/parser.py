@@ -20,6 +20,15 @@ AST nodes are plain tuples (hashable, trivially serialisable):
   ('and', a, b) ; ('or', a, b) ; ('tern', c, a, b)
   ('comp', kind, target, vars, args)   comprehension macros
   ('bind', var, init, body)            cel.bind(var, init, body)
+
+With optional syntax (cel-go parser.EnableOptionalSyntax, which the reference's environment turns on through
+cel.OptionalTypes(), ``internal/conditions/cel.go:71``):
+
+  ('optsel', operand, field)        operand.?field
+  ('optindex', operand, index)      operand[?index]
+  ('optelem', x)                    [?x] as a list element; {k: ?x} stands for the map entry {?k: x}
+  o.optMap(v, e) / o.optFlatMap(v, e) expand as cel-go's macros do, into
+  o.hasValue() ? optional.of(cel.bind(v, o.value(), e)) : optional.none() (optFlatMap: without optional.of)
 """
 from __future__ import annotations
 
@@ -209,9 +218,10 @@ def tokenize(src: str):
 
 
 class _Parser:
-    def __init__(self, src: str):
+    def __init__(self, src: str, optional_syntax=False):
         self.toks = tokenize(src)
         self.i = 0
+        self.optional_syntax = optional_syntax
 
     def peek(self):
         return self.toks[self.i]
@@ -334,7 +344,19 @@ class _Parser:
                 self.expect("]")
                 e = ("index", e, idx)
             elif self.at(".?") or self.at("[?"):
-                raise CELSyntaxError("optional field selection is not supported")
+                if not self.optional_syntax:
+                    raise CELSyntaxError("optional field selection is not supported")
+                if self.accept(".?"):
+                    t = self.peek()
+                    if t[0] != "ident":
+                        raise CELSyntaxError(f"expected field name, got {t!r}")
+                    self.i += 1
+                    e = ("optsel", e, t[1])
+                else:
+                    self.i += 1
+                    idx = self.expr()
+                    self.expect("]")
+                    e = ("optindex", e, idx)
             else:
                 return e
 
@@ -352,6 +374,24 @@ class _Parser:
             self.expect(close)
             return out
 
+    def list_elems(self, first_opt=False):
+        """A list literal's elements, `?e` marking an optional one (cel-go: included when e has a value).  `[?` is one token:
+        first_opt says that it opened the list."""
+        out = []
+        if not first_opt and self.accept("]"):
+            return out
+        while True:
+            opt = first_opt or self.accept("?")
+            first_opt = False
+            x = self.expr()
+            out.append(("optelem", x) if opt else x)
+            if self.accept(","):
+                if self.accept("]"):
+                    return out
+                continue
+            self.expect("]")
+            return out
+
     def method(self, target, name, args):
         if name in _COMP_MACROS and len(args) in _COMP_MACROS[name]:
             nvars = 1
@@ -367,6 +407,12 @@ class _Parser:
         # the evaluator resolves e.g. ('call','contains',('ident','sets'),...) .
         if name == "bind" and target == ("ident", "cel") and len(args) == 3 and args[0][0] == "ident":
             return ("bind", args[0][1], args[1], args[2])
+        if self.optional_syntax and name in ("optMap", "optFlatMap") and len(args) == 2 and args[0][0] == "ident":
+            # cel-go's optional macros (checker/optional.go): the body sees the value bound to the variable
+            body = ("bind", args[0][1], ("call", "value", target, ()), args[1])
+            if name == "optMap":
+                body = ("call", "of", ("ident", "optional"), (body,))
+            return ("tern", ("call", "hasValue", target, ()), body, ("call", "none", ("ident", "optional"), ()))
         return ("call", name, target, tuple(args))
 
     def primary(self):
@@ -400,16 +446,22 @@ class _Parser:
                 return e
             if t[1] == "[":
                 self.i += 1
+                if self.optional_syntax:
+                    return ("list", tuple(self.list_elems()))
                 return ("list", tuple(self.args("]")))
+            if t[1] == "[?" and self.optional_syntax:
+                self.i += 1
+                return ("list", tuple(self.list_elems(first_opt=True)))
             if t[1] == "{":
                 self.i += 1
                 entries = []
                 if not self.accept("}"):
                     while True:
+                        opt = self.optional_syntax and self.accept("?")
                         kx = self.expr()
                         self.expect(":")
                         vx = self.expr()
-                        entries.append((kx, vx))
+                        entries.append((kx, ("optelem", vx) if opt else vx))
                         if self.accept(","):
                             if self.accept("}"):
                                 break
@@ -429,10 +481,11 @@ _CACHE: dict = {}
 
 def parse(src: str):
     """Parse CEL source text to an AST (cached by text, like the reference's
-    ``ProgramCache`` keyed by ``Expr.Original``, ruletable.go:518-559)."""
+    ``ProgramCache`` keyed by ``Expr.Original``, ruletable.go:518-559).  Optional syntax is on, as in the
+    reference's environment (cel.OptionalTypes())."""
     ast = _CACHE.get(src)
     if ast is None:
-        ast = _Parser(src).parse()
+        ast = _Parser(src, optional_syntax=True).parse()
         _CACHE[src] = ast
     return ast
 
@@ -448,9 +501,9 @@ def walk(ast):
         k = n[0]
         if k in ("lit", "ident"):
             continue
-        if k in ("select", "has"):
+        if k in ("select", "has", "optsel", "optelem"):
             stack.append(n[1])
-        elif k == "index":
+        elif k in ("index", "optindex"):
             stack.extend((n[2], n[1]))
         elif k == "call":
             stack.extend(reversed(n[3]))

@@ -420,7 +420,12 @@ enum CbhOp {
 enum CbhExtFn { MF_ABS = 0, MF_SIGN = 1, MF_CEIL = 2, MF_FLOOR = 3, MF_ROUND = 4, MF_TRUNC = 5, MF_SQRT = 6, MF_ISNAN = 7, MF_ISINF = 8,
                 MF_ISFINITE = 9, MF_BITNOT = 10, MF_BITAND = 11, MF_BITOR = 12, MF_BITXOR = 13, MF_SHL = 14, MF_SHR = 15,
                 MF_GREATEST = 16, MF_LEAST = 17,   // greatest / least: one list argument, or 1 .. N numbers
-                XF_SPLIT = 18 };                   // s.split(sep) (2 arguments) / s.split(sep, n) (3)
+                XF_SPLIT = 18,                     // s.split(sep) (2 arguments) / s.split(sep, n) (3)
+                // cel-go optional values, which the lowering keeps as a pair (presence, value) of expressions (cbh_vm.h opt_op):
+                XF_OPT_HAS = 19,       // pop key, container -> is key present: a map's string key, a list's int index in range
+                XF_OPT_VALUE = 20,     // pop value, presence -> value if present, else CBH_ERR_OPT_NONE (o.value())
+                XF_OPT_NONZERO = 21,   // TOS -> is it not its type's zero value (optional.ofNonZeroValue)
+                XF_OPT_OK = 22 };      // TOS -> true unless an error (the presence of optional.of(x))
 enum CbhIterKind { IT_ALL = 0, IT_EXISTS = 1, IT_EXISTS_ONE = 2, IT_FILTER = 3, IT_MAP = 4,   // filter / map build a list in the lane's arena
                    IT_MAP_FILTER = 5 };   // map(x, pred, expr) / transformList(i, v, pred, expr): the body leaves pred and expr
 #define CBH_ARENA_ENTRIES 48u   /* values per lane a program may build lists from; more marks the tuple CBH_ST_UNSUPPORTED */

@@ -1615,6 +1615,7 @@ static int trace_decode(const cbi_table* t, const cbi_batch* b, const cbh_result
       case CBH_ERR_UINT_OVERFLOW: return "unsigned integer overflow";
       case CBH_ERR_NEG_SHIFT:   // cel-go ext/math.go: detail bit 0 = bitShiftRight, the rest the offset's magnitude
         return std::string("math.bitShift") + ((detail & 1) ? "Right" : "Left") + "() negative offset: -" + std::to_string(detail >> 1);
+      case CBH_ERR_OPT_NONE: return "optional.none() dereference";
       case CBH_ERR_NO_SUCH_KEY: return "no such key: " + std::string(str(detail & 0xFFFFFFFFu));
       case CBH_ERR_UNDEFINED_FIELD: if (detail >= t->trace_strings.size()) throw TraceIncomplete{}; return "undefined field '" + t->trace_strings[detail] + "'";
       case CBH_ERR_EDR_FAILED: {

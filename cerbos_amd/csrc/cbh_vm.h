@@ -1130,6 +1130,40 @@ __device__ inline SlowVal math_op(const Ctx& c, u32 fn, u32 n, int base) {
   return bad;
 }
 
+// cel-go optional values (XF_OPT_*): the lowering keeps an optional as two expressions, its presence and its value (lower/celc.py
+// _opt), so no optional ever sits on the operand stack; these are the few steps it cannot spell with existing opcodes.  A case
+// cel-go's behaviour is not pinned for here - an optional qualifier on a value that is neither a map with string keys nor a list
+// indexed by an int, the zero value of a type other than null / bool / numbers / string / list / map - flags the tuple.
+__device__ inline SlowVal opt_op(const Ctx& c, u32 fn, u32 n, int base) {
+  const Val x = mk(ST(base), SV(base)), y = n > 1 ? mk(ST(base + 1), SV(base + 1)) : x;
+  if (x.t == CBH_T_ERR) return SlowVal{x.t, 0, x.v};
+  const SlowVal flag{CBH_T_ERR, CBH_ST_UNSUPPORTED, 0};
+  if (fn == XF_OPT_OK && n == 1) return SlowVal{CBH_T_BOOL, 0, 1};
+  if (fn == XF_OPT_VALUE && n == 2) {
+    if (x.t != CBH_T_BOOL) return SlowVal{CBH_T_ERR, 0, (u64)CBH_ERR_NO_SUCH_OVERLOAD};
+    return x.v ? SlowVal{y.t, 0, y.v} : SlowVal{CBH_T_ERR, 0, (u64)CBH_ERR_OPT_NONE};
+  }
+  if (fn == XF_OPT_NONZERO && n == 1) {
+    u64 nz;
+    switch (x.t) {
+      case CBH_T_NULL: nz = 0; break;
+      case CBH_T_BOOL: case CBH_T_INT: case CBH_T_UINT: nz = x.v != 0; break;
+      case CBH_T_DOUBLE: nz = as_f64(x.v) != 0.0; break;
+      case CBH_T_STRING: { gbytes p; u32 len; str_span(c, (u32)x.v, p, len); nz = len != 0; break; }
+      case CBH_T_LIST: case CBH_T_MAP: nz = cont_len(x.v) != 0; break;
+      default: return flag;
+    }
+    return SlowVal{CBH_T_BOOL, 0, nz};
+  }
+  if (fn == XF_OPT_HAS && n == 2) {
+    if (y.t == CBH_T_ERR) return SlowVal{y.t, 0, y.v};
+    if (x.t == CBH_T_MAP && y.t == CBH_T_STRING) { Val out; return SlowVal{CBH_T_BOOL, 0, (u64)map_find(c, x, y, out)}; }
+    if (x.t == CBH_T_LIST && y.t == CBH_T_INT) return SlowVal{CBH_T_BOOL, 0, (u64)((i64)y.v >= 0 && (i64)y.v < (i64)cont_len(x.v))};
+    return flag;
+  }
+  return SlowVal{CBH_T_ERR, 0, (u64)CBH_ERR_NO_SUCH_OVERLOAD};
+}
+
 // The extension functions on request values (cbh_blob.h OP_LISTFN, arg >= 0x100), out of line and by value like rope_op: `a` = function (CbhExtFn)
 // | argument count << 8; the arguments are the top `a >> 8` entries of the lane's operand stack (`sp` = its depth), the first one
 // deepest; `ap` = the fill of the lane's arena.  -> the result, the CBH_ST_* bits to raise in status bits 0..15 and the arena's new
@@ -1142,6 +1176,7 @@ __device__ SlowVal ext_op(const KernelArgs* ka, const VmLds lds, u32 a, int sp, 
   const u32 fn = a & 0xFFu, n = a >> 8;
   if (n == 0 || (int)n > sp) return SlowVal{CBH_T_ERR, ap << 16, (u64)CBH_ERR_NO_SUCH_OVERLOAD};
   const int base = sp - (int)n;
+  if (fn >= XF_OPT_HAS) { SlowVal r = opt_op(c, fn, n, base); r.status |= ap << 16; return r; }
   if (fn != XF_SPLIT) { SlowVal r = math_op(c, fn, n, base); r.status = ap << 16; return r; }
   const Val x = mk(ST(base), SV(base)), sep = n > 1 ? mk(ST(base + 1), SV(base + 1)) : mk_err(),
             lim = n > 2 ? mk(ST(base + 2), SV(base + 2)) : mk(CBH_T_INT, ~0ull);

@@ -94,6 +94,7 @@ _MATH_FNS = {"abs": (0, 1), "sign": (1, 1), "ceil": (2, 1), "floor": (3, 1), "ro
              "isNaN": (7, 1), "isInf": (8, 1), "isFinite": (9, 1), "bitNot": (10, 1), "bitAnd": (11, 2), "bitOr": (12, 2),
              "bitXor": (13, 2), "bitShiftLeft": (14, 2), "bitShiftRight": (15, 2), "greatest": (16, None), "least": (17, None)}
 XF_SPLIT = 18
+XF_OPT_HAS, XF_OPT_VALUE, XF_OPT_NONZERO, XF_OPT_OK = 19, 20, 21, 22   # cel-go optional values (cbh_vm.h opt_op)
 LOCAL_BIND_STORE, LOCAL_BIND_END = 0x100, 0x200   # OP_LOCAL's cel.bind forms
 
 
@@ -132,10 +133,12 @@ def _subst(ast, fn):
     k = ast[0]
     if k in ("lit", "ident"):
         return fn(ast)
-    if k in ("select", "has"):
+    if k in ("select", "has", "optsel"):
         return fn((k, _subst(ast[1], fn), ast[2]))
-    if k == "index":
+    if k in ("index", "optindex"):
         return fn((k, _subst(ast[1], fn), _subst(ast[2], fn)))
+    if k == "optelem":
+        return fn((k, _subst(ast[1], fn)))
     if k == "call":
         tgt = None if ast[2] is None else _subst(ast[2], fn)
         return fn((k, ast[1], tgt, tuple(_subst(a, fn) for a in ast[3])))
@@ -525,7 +528,7 @@ class ProgramBuilder:
         for _name, text in params.ordered_variables:
             fc.cur_text = text
             d0 = fc.depth
-            fc.expr(params.inline(celparser.parse(text)))
+            fc.expr(_failure_probe(params.inline(celparser.parse(text))))
             assert fc.depth == d0 + 1
             fc.emit(OP_LEAF)
             fc.emit(OP_POP, 0, -1)
@@ -596,7 +599,7 @@ class ProgramBuilder:
             def build(text=text):
                 fc = _FuncCompiler(self, params, True, trace=True)
                 fc.cur_text = text
-                fc.value_expr(params.inline(celparser.parse(text)))
+                fc.value_expr(_failure_probe(params.inline(celparser.parse(text))))
                 fc.emit(OP_LEAF, self.tid(text) + 1)
                 return fc
             out.append(self._trace_compile(("trace-var", text, params.key()), build))
@@ -779,6 +782,70 @@ def _is_const(ast):
     return False
 
 
+# ---- cel-go optional values (cel.OptionalTypes(), internal/conditions/cel.go:71)
+# No optional value ever reaches the device.  The lowering keeps one as a pair of expressions - its PRESENCE (a bool that errs
+# exactly when the optional does) and its VALUE (read only where the presence is true) - and spells what the consumer does with
+# them: o.hasValue() is the presence, o.orValue(d) the ternary `presence ? value : d`, o.value() an XF_OPT_VALUE step that
+# answers CBH_ERR_OPT_NONE on none.  An optional used any other way (as an output, a list element, a function's argument, compared
+# with a plain value) is flagged.
+_TRUE, _FALSE = ("lit", "bool", True), ("lit", "bool", False)
+_NONE_VALUE = ("call", "__error__", None, ())   # the value of optional.none(): never selected
+
+
+def _xf(fn, *args):
+    """An OP_LISTFN extension step (cbh_vm.h ext_op) on the values of `args`."""
+    return ("call", "__xf__", None, (("lit", "int", fn),) + tuple(args))
+
+
+def _is_opt(ast):
+    """Is the value of `ast` an optional (syntactically, as cel-go's checker types it)?"""
+    k = ast[0]
+    if k in ("optsel", "optindex"):
+        return True
+    if k in ("select", "index"):
+        return _is_opt(ast[1])
+    if k == "call":
+        name, tgt, args = ast[1], ast[2], ast[3]
+        if tgt == ("ident", "optional"):
+            return name in ("of", "ofNonZeroValue") and len(args) == 1 or name == "none" and not args
+        return name == "or" and tgt is not None and len(args) == 1 and _is_opt(tgt)
+    if k == "tern":
+        return _is_opt(ast[2]) or _is_opt(ast[3])
+    if k == "bind":
+        return _is_opt(_unbind_opt(ast)[3])
+    if k == "varscope":
+        return _is_opt(ast[2])
+    return False
+
+
+def _failure_probe(ast):
+    """What a variable's failure probe evaluates: an optional's presence, which errs exactly when the optional does."""
+    return ("call", "hasValue", ast, ()) if _is_opt(ast) else ast
+
+
+def _subst_ident(ast, name, repl):
+    """`ast` with the free occurrences of identifier `name` replaced by `repl`."""
+    k = ast[0]
+    if k == "ident":
+        return repl if ast[1] == name else ast
+    if k == "bind":
+        body = ast[3] if ast[1] == name else _subst_ident(ast[3], name, repl)
+        return ("bind", ast[1], _subst_ident(ast[2], name, repl), body)
+    if k == "comp":
+        args = ast[4] if name in ast[3] else tuple(_subst_ident(a, name, repl) for a in ast[4])
+        return ("comp", ast[1], _subst_ident(ast[2], name, repl), ast[3], args)
+    kids = celfold._children(ast)
+    return celfold._rebuild(ast, [_subst_ident(c, name, repl) for c in kids]) if kids else ast
+
+
+def _unbind_opt(ast):
+    """cel.bind(v, o, body) with an optional o: the body reads o itself wherever it names v.  The bind that stays holds o's
+    presence in a slot nobody reads, so that an erring o is still the result whatever the body does."""
+    if ast[0] != "bind" or not _is_opt(ast[2]):
+        return ast
+    return ("bind", "\0" + ast[1], ("call", "hasValue", ast[2], ()), _subst_ident(ast[3], ast[1], ast[2]))
+
+
 class _FuncCompiler:
     def __init__(self, pb: ProgramBuilder, params: Params, allow_runtime: bool, trace=False):
         self.pb = pb
@@ -861,11 +928,17 @@ class _FuncCompiler:
             self.emit(OP_CONST, self.pb.const(T_BOOL, 1), +1)
             return
         op = c[0]
+        if op == "leaf":   # a fused leaf of _opt_leaf_tree
+            assert self._fused_leaf(c[1]), c[1]
+            return
         if op == "expr":
             self.cur_text = c[1]
             ast = self.params.inline(celparser.parse(c[1]))
             if not self.trace and self._fused_leaf(ast):
                 return
+            tree = None if self.trace else self._opt_leaf_tree(ast)
+            if tree is not None:
+                return self.cond(tree)
             d0 = self.depth
             self.expr(ast)
             assert self.depth == d0 + 1, (c[1], self.depth, d0)
@@ -934,6 +1007,68 @@ class _FuncCompiler:
         self.word(a[1])
         self.word(b[1])
         return True
+
+    def _opt_root_key(self, o):
+        """`P|R.attr.?x` / `request.auxData.jwt.?x` (or `[?"x"]`) -> the presence leaf `"x" in <the attribute map>`, else None."""
+        if o[0] not in ("optsel", "optindex") or o[1][0] not in ("select", "index"):
+            return None
+        key = o[2] if o[0] == "optsel" else (o[2][2] if o[2][0] == "lit" and o[2][1] == "string" else None)
+        p = self._path(o[1])
+        if key is None or p is None or p[0] != "col" or p[1] not in ("P", "R", "J") or p[2]:
+            return None
+        return ("bin", "in", ("lit", "string", key), o[1]), ("select", o[1], key)
+
+    def _opt_leaf_tree(self, ast):
+        """The hot forms of optional syntax as a condition tree of fused leaves, which the flat kernels evaluate inline
+        (cbh_check_flat.h flat_tree), instead of a generic program:
+          P|R.attr.?x.hasValue()            -> the leaf `"x" in P|R.attr`
+          P|R.attr.?x.orValue(c) <op> k     -> all(has, x <op> k) when `c <op> k` folds to false, any(none(has), x <op> k) when
+                                               it folds to true; with k a column or the principal id,
+                                               any(all(has, x <op> k), all(none(has), c <op> k)).
+        The attribute maps are maps whatever the request holds, so `has` never errs and the tree decides as the expression does.
+        None: not one of these forms."""
+        if self.locals:
+            return None
+        if ast[0] == "call" and ast[1] == "hasValue" and ast[2] is not None and not ast[3]:
+            rk = self._opt_root_key(ast[2])
+            return ("leaf", rk[0]) if rk is not None and self._leafable(rk[0]) else None
+        if ast[0] != "bin" or ast[1] not in _BINOPS or ast[1] in ("+", "-", "*", "/", "%"):
+            return None
+        for side in (2, 3):
+            o = ast[side]
+            if not (o[0] == "call" and o[1] == "orValue" and o[2] is not None and len(o[3]) == 1 and _is_const(o[3][0])):
+                continue
+            rk = self._opt_root_key(o[2])
+            if rk is None:
+                continue
+            has, col = rk
+
+            def with_(x):
+                return ("bin", ast[1], x, ast[5 - side]) if side == 2 else ("bin", ast[1], ast[2], x)
+            present, absent = with_(col), with_(o[3][0])
+            if not self._leafable(has) or not self._leafable(present):
+                return None
+            other = ast[5 - side]
+            if _is_const(other):
+                folded = celfold.fold(absent)
+                if folded[0] != "lit" or folded[1] != "bool":
+                    return None   # c <op> k errs (or is not folded): the generic program decides it
+                if folded[2]:
+                    return ("any", [("none", [("leaf", has)]), ("leaf", present)])
+                return ("all", [("leaf", has), ("leaf", present)])
+            if not self._leafable(absent):
+                return None
+            return ("any", [("all", [("leaf", has), ("leaf", present)]), ("all", [("none", [("leaf", has)]), ("leaf", absent)])])
+        return None
+
+    def _leafable(self, ast):
+        """Would _fused_leaf take `ast`?  (Asked without emitting: the operands' columns and constants are interned either way.)"""
+        if ast[0] != "bin" or ast[1] not in ("==", "!=", "<", "<=", ">", ">=", "in"):
+            return False
+        lhs, rhs = ast[2], ast[3]
+        if ast[1] != "in":
+            lhs, rhs = _int_lit_as_double(lhs), _int_lit_as_double(rhs)
+        return self._simple_operand(lhs) is not None and self._simple_operand(rhs) is not None
 
     def value_expr(self, ast):
         """An expression whose VALUE is wanted (a part of an output expression, a variable's definition - trace programs).  As
@@ -1026,6 +1161,14 @@ class _FuncCompiler:
     def _expr(self, ast):  # noqa: C901
         k = ast[0]
         pb = self.pb
+        if k in ("call", "bin", "bind"):
+            if k == "bind" and _is_opt(ast[2]):
+                return self._expr(_unbind_opt(ast))
+            sub = self._opt_consumer(ast)
+            if sub is not None:
+                return self._expr(sub)
+        if _is_opt(ast) or k == "optelem":
+            return self.unsupported("an optional value used as a value")
         if k == "lit" or ((k == "list" or k == "map") and _is_const(ast)):
             try:
                 t, v = pb._heap_value(ast)
@@ -1166,6 +1309,82 @@ class _FuncCompiler:
             return self._bind(ast)
         return self.unsupported("%s expression" % k)
 
+    def _opt(self, ast):
+        """An optional-valued expression -> (presence, value) as two ASTs (see _is_opt above).  cel-go interpreter/attributes.go:
+        from the first optional qualifier of a select / index chain on, a qualifier only tests for presence; the ones before it
+        keep their error."""
+        k = ast[0]
+        if k in ("optsel", "optindex", "select", "index"):
+            key = ("lit", "string", ast[2]) if k in ("optsel", "select") else ast[2]
+            base, plain = ast[1], "select" if k in ("optsel", "select") else "index"
+            if _is_opt(base):
+                bp, bv = self._opt(base)
+                return ("tern", bp, self._present(bv, key), _FALSE), (plain, bv, ast[2])
+            return self._present(base, key), (plain, base, ast[2])
+        if k == "call":
+            name, tgt, args = ast[1], ast[2], ast[3]
+            if tgt == ("ident", "optional"):
+                if name == "none":
+                    return _FALSE, _NONE_VALUE
+                x = args[0]
+                if name == "of":
+                    return (_TRUE if _is_const(x) else _xf(XF_OPT_OK, x)), x
+                self.pb.reads_string_bytes = True
+                return _xf(XF_OPT_NONZERO, x), x
+            if name == "or":
+                if not _is_opt(args[0]):
+                    raise _Unsupported("or() with a value that is not an optional")
+                p1, v1 = self._opt(tgt)
+                p2, v2 = self._opt(args[0])
+                return ("tern", p1, _TRUE, p2), ("tern", p1, v1, v2)
+        if k == "tern":
+            if not (_is_opt(ast[2]) and _is_opt(ast[3])):
+                raise _Unsupported("a conditional between an optional and a value")
+            pa, va = self._opt(ast[2])
+            pb_, vb = self._opt(ast[3])
+            return ("tern", ast[1], pa, pb_), ("tern", ast[1], va, vb)
+        if k == "bind":
+            ast = _unbind_opt(ast)
+            p, v = self._opt(ast[3])
+            return ("bind", ast[1], ast[2], p), ("bind", ast[1], ast[2], v)
+        if k == "varscope":
+            return self._opt(ast[2])
+        raise _Unsupported("optional %s" % k)
+
+    def _present(self, container, key):
+        """Is `key` present in `container` (an optional qualifier)?  A single key of P.attr / R.attr / auxData.jwt - maps
+        whatever the request holds - is the column's presence; anything else asks XF_OPT_HAS, which flags an operand that is
+        neither a map nor a list."""
+        if key[0] == "lit" and key[1] == "string" and container[0] in ("select", "index"):
+            p = self._path(container)
+            if p is not None and p[0] == "col" and p[1] in ("P", "R", "J") and not p[2]:
+                return ("has", container, key[2])
+        return _xf(XF_OPT_HAS, container, key)
+
+    def _opt_consumer(self, ast):
+        """o.hasValue() / o.value() / o.orValue(d) / o1 == o2 / o1 != o2 -> the AST that computes it from o's presence and
+        value, or None when `ast` is not one of them."""
+        try:
+            if ast[0] == "call" and ast[2] is not None and _is_opt(ast[2]):
+                name, n = ast[1], len(ast[3])
+                if name in ("hasValue", "value", "orValue") and n == (name == "orValue"):
+                    p, v = self._opt(ast[2])
+                    if name == "hasValue":
+                        return p
+                    if name == "value":
+                        return _xf(XF_OPT_VALUE, p, v)
+                    return ("tern", p, v, ast[3][0])
+            if ast[0] == "bin" and ast[1] in ("==", "!=") and (_is_opt(ast[2]) or _is_opt(ast[3])):
+                if not (_is_opt(ast[2]) and _is_opt(ast[3])):
+                    return ("call", "__unsupported_opt__", None, ())
+                p1, v1 = self._opt(ast[2])
+                p2, v2 = self._opt(ast[3])
+                eq = ("tern", p1, ("tern", p2, ("bin", "==", v1, v2), _FALSE), ("not", p2))
+                return eq if ast[1] == "==" else ("not", eq)
+        except _Unsupported:
+            return ("call", "__unsupported_opt__", None, ())
+        return None
+
     def _bind(self, ast):
         """cel.bind(v, init, body) whose init reads the request (a constant one was substituted by the folding): init is evaluated
         once and stored in a local slot - the slots comprehension variables use, CBH_MAX_LOCALS of them - that `v` reads in the body.
@@ -1191,6 +1410,12 @@ class _FuncCompiler:
             self.emit(OP_CONST, self.pb.const(T_NULL, 0), +1)
             self.emit(OP_NEG)
             return self.emit(OP_VARSCOPE, self.pb.tid(args[0][2]))
+        if name == "__unsupported_opt__":
+            return self.unsupported("an optional value used as a value")
+        if name == "__xf__":   # an extension step the lowering spells itself (optional values, _opt)
+            for x in args[1:]:
+                self._expr(x)
+            return self.emit(OP_LISTFN, args[0][2] | ((len(args) - 1) << 8), 2 - len(args))
         if name == "__error__":
             # evaluates to a CEL error without marking the tuple unsupported
             self.emit(OP_CONST, self.pb.const(T_NULL, 0), +1)

@@ -24,14 +24,15 @@ class _LocalList:
         self.n = n
 TR_DRFAIL = 32   # cbh_check_wave.h CBH_TR_DRFAIL
 (ERR_OTHER, ERR_NO_SUCH_KEY, ERR_ATTR_MISSING, ERR_NO_SUCH_OVERLOAD, ERR_UNDEFINED_FIELD, ERR_DIV_BY_ZERO, ERR_MOD_BY_ZERO,
- ERR_INT_OVERFLOW, ERR_UINT_OVERFLOW, ERR_EDR_FAILED, ERR_NEG_SHIFT) = range(11)
+ ERR_INT_OVERFLOW, ERR_UINT_OVERFLOW, ERR_EDR_FAILED, ERR_NEG_SHIFT, ERR_OPT_NONE) = range(12)
 T_NULL, T_BOOL, T_INT, T_UINT, T_DOUBLE, T_STRING, T_LIST, T_MAP, T_TIMESTAMP, T_DURATION = range(10)
 T_EDRSET = 11   # include/cerbos_hip.h CBH_T_EDRSET
 HEAP_TABLE, HEAP_ROLES = 0, 2
 RECORD_WORDS = 8
 
 _FIXED = {ERR_NO_SUCH_OVERLOAD: "no such overload", ERR_DIV_BY_ZERO: "division by zero", ERR_MOD_BY_ZERO: "modulus by zero",
-          ERR_INT_OVERFLOW: "integer overflow", ERR_UINT_OVERFLOW: "unsigned integer overflow"}
+          ERR_INT_OVERFLOW: "integer overflow", ERR_UINT_OVERFLOW: "unsigned integer overflow",
+          ERR_OPT_NONE: "optional.none() dereference"}
 
 
 class _Incomplete(Exception):

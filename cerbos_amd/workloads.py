@@ -85,6 +85,21 @@ def c2_policies():
     return [{"apiVersion": API, "resourcePolicy": rp}]
 
 
+C2_OPTIONAL = {"R.attr.public == true": "R.attr.?public.orValue(false) == true",
+               "R.attr.owner == P.id": 'R.attr.?owner.orValue("") == P.id',
+               "R.attr.amount > 1000": "R.attr.?amount.orValue(0) > 1000",
+               "P.attr.department == R.attr.department": 'P.attr.?department.orValue("") == R.attr.department',
+               'R.attr.status in ["CLOSED", "ARCHIVED"]': 'R.attr.?status.orValue("OPEN") in ["CLOSED", "ARCHIVED"]'}
+
+
+def c2_optional_policies():
+    """C2 with every condition written in CEL optional syntax, a missing attribute defaulted (tools/bench_optional_c2.py)."""
+    docs = c2_policies()
+    for r in docs[0]["resourcePolicy"]["rules"]:
+        r["condition"] = _expr(C2_OPTIONAL[r["condition"]["match"]["expr"]])
+    return docs
+
+
 def c2_requests(n_requests=250_000, seed=2, actions_per_request=4):
     rng = np.random.default_rng(seed)
     n = n_requests

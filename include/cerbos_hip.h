@@ -433,6 +433,7 @@ int cbh_wire_check_requests_trail_pb(cbh_table* t, uint32_t device_index, const 
                                     /* the whole payload, code in the low byte) = mask of the failed roles, bit = edr_mask bit       */
 #define CBH_ERR_NEG_SHIFT 10u       /* "math.bitShiftLeft() negative offset: -<n>"; detail bit 0 = bitShiftRight, bits 1.. = n (the */
                                     /* offset's magnitude, below 2^55)                                                              */
+#define CBH_ERR_OPT_NONE 11u        /* "optional.none() dereference" */
 #define CBH_TRACE_RECORD_WORDS 8u
 
 typedef struct cbh_trace {
