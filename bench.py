@@ -9,15 +9,21 @@ one sweep of the decision kernels over the whole set (one launch per 1M-tuple ba
 driver's 20 steps keep the GPU busy for ~50 ms).
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does what `value` needs and no more: it sets up, warms up, times the steps and prints the line (after writing
+the dump of --dump-outputs).  `--full` adds everything else this script measures and checks, after the timed region: the
+one-stream leg (`roofline.serial`), the latency, PCIe-inclusive and wire-inclusive legs, north_star's target set (`target_T`)
+and the CPU baseline with its oracle checks (`cpu_baseline`); `--no-side-legs` / `--no-cpu-baseline` take parts of it away again.
 
 Launches of different batches overlap on the device: resident batches are dealt to a few streams at upload
 (cbh_table_set_resident_streams, default 4), so one launch's dispatch ramp fills what another's drain leaves idle.
 `roofline.achieved` is therefore the rate the device sustains over the timed region; `roofline.kernel_ms` the average
-begin-to-end time of one launch inside it; `roofline.serial` the same launches strictly one after the other on one stream.
+begin-to-end time of one launch inside it; `roofline.serial` (--full) the same launches strictly one after the other on one stream.
 
-Three rates, side by side in the line (the third: `wire_inclusive_decisions_per_s`, serialized CheckInputs in, serialized
+Under --full, three rates side by side in the line (the third: `wire_inclusive_decisions_per_s`, serialized CheckInputs in, serialized
 CheckOutputs out by the device road, one host thread - what a server delivers): `value` = `resident_decisions_per_s`, the whole-job decision rate with the inputs
 already resident in HBM when the timed region starts (what the kernel roofline is computed from), and
 `pcie_inclusive_decisions_per_s`, SURVEY.md §8(d)'s service-level metric (1): the wall time of cbh_check_batch INCLUDING
@@ -121,21 +127,28 @@ def main():
     ap.add_argument("--replicas", type=int, default=None,
                     help="device copies of every seeded batch, each at its own HBM address and launched separately (default: 4 for C2, "
                          "so that a sweep is 128 launches over 6.4 GB and a 20-step run keeps the GPU busy for ~50 ms; 1 otherwise)")
-    ap.add_argument("--cpu-sample", type=int, default=100_000, help="requests timed through the CPU oracle (~15 s)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-side-legs", action="store_true", help="skip the PCIe-inclusive / latency legs (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run every other measurement and check: the one-stream leg, the latency / PCIe- / "
+                         "wire-inclusive legs, the target set T and the CPU baseline with its oracle checks (a plain run times `value` alone)")
+    ap.add_argument("--cpu-sample", type=int, default=100_000, help="requests timed through the CPU oracle (~15 s; --full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and its oracle checks")
+    ap.add_argument("--no-side-legs", action="store_true", help="with --full: skip the one-stream, PCIe-inclusive / latency legs and target_T (profiling runs)")
     ap.add_argument("--audit-trail", action="store_true",
                     help="measurement aid: every launch also keeps AuditTrail.EffectivePolicies (cbh_batch_set_trail, the trail forms of the "
                          "decision kernels: what a server with decision logs on pays); implies --no-side-legs except the one-stream leg")
-    ap.add_argument("--serial-leg", action="store_true", help="measurement aid: keep the one-stream leg (the kernel by itself) under --no-side-legs")
+    ap.add_argument("--serial-leg", action="store_true",
+                    help="measurement aid: run the one-stream leg (the kernel by itself) without the other side legs (a plain run, or --no-side-legs)")
     ap.add_argument("--check-first", action="store_true",
-                    help="measurement aid (A/B runs): with --no-cpu-baseline, still compare every tuple of the first batch with oracle/ccheck.cpp after the timed region")
+                    help="measurement aid (A/B runs): without the CPU baseline (a plain run, or --no-cpu-baseline), still compare every tuple of the "
+                         "first batch with oracle/ccheck.cpp after the timed region")
     ap.add_argument("--inproc-gpus", type=int, default=0, help="also time one engine over this many devices in THIS process")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write a fixed seeded sample of what the last step computed as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    side_legs = args.full and not args.no_side_legs        # (--audit-trail keeps only the one-stream leg of them, below)
+    cpu_baseline = args.full and not args.no_cpu_baseline
 
     # stdout carries exactly one JSON line.  RCCL writes its banner and its warnings to file descriptor 1 from its own threads
     # (seen: a warning landing in the middle of the line), so everything else that writes there is sent to stderr and the
@@ -223,6 +236,7 @@ def main():
     cr0 = batch0 = None
     dbatches, tuples_per_batch, resident_bytes = [], None, 0
     by_replica = [[] for _ in range(replicas)]
+    want_serial = rank == 0 and (side_legs or args.serial_leg)
     serial_host = []   # host batches kept for the one-stream leg (rank 0)
     for k in range(n_seeded):
         cr = wl[1](n_requests, seed=base_seed + 1000 * k + rank)
@@ -231,7 +245,7 @@ def main():
             cr0, batch0 = cr, batch
             tuples_per_batch = batch.n_tuples
         assert batch.n_tuples == tuples_per_batch
-        if rank == 0 and len(serial_host) < SERIAL_BATCHES:
+        if want_serial and len(serial_host) < SERIAL_BATCHES:
             serial_host.append(batch)
         nbytes = sum(getattr(batch, f).nbytes for f in ("req_u32", "roles", "tuple_action", "col_tag", "col_val", "heap_tag",
                                                          "heap_val", "str_off", "str_bytes", "str_flags")) + 10 * batch.n_tuples + 8 * batch.n_requests
@@ -288,7 +302,7 @@ def main():
     # copies of the first batches of the set - in the timed region above launches of different batches overlap on the
     # device, which lengthens each one's begin-to-end time while shortening the sweep
     serial = None
-    if rank == 0 and streams > 1 and (not args.no_side_legs or args.serial_leg):
+    if want_serial and streams > 1:
         table.set_resident_streams(1)
         sdb = [table.upload(hb) for hb in serial_host]
         if args.audit_trail:
@@ -314,11 +328,11 @@ def main():
 
     side = {}
     if args.audit_trail:
-        args.no_side_legs = True   # (the one-shot legs have no trail to keep)
+        side_legs = False   # (the one-shot legs have no trail to keep)
         if rank == 0:
             from cerbos_amd.engine import effective_policy_keys
             side["effective_policies_of_batch_0"] = len(effective_policy_keys(lt.policy_keys, table.trail(dbatches[0])[0]))
-    if rank == 0 and not args.no_side_legs:
+    if rank == 0 and side_legs:
         # per-launch latency distribution (each launch synchronised; outside the timed region)
         lat = []
         for k in range(min(40, 4 * n_batches)):
@@ -480,10 +494,10 @@ def main():
             side["wire_inclusive_error"] = str(e)[:300]
 
     # north_star's own target configuration (100 policies / 10k rules with CEL conditions, 1M tuples per launch), timed in THIS
-    # run whatever workload the line is quoted on: resident sweeps over 8 seeded batches, the kernel by itself on one stream, and
+    # run (--full) whatever workload the line is quoted on: resident sweeps over 8 seeded batches, the kernel by itself on one stream, and
     # every tuple of the first batch against oracle/ccheck.cpp (the checker, after the timed region)
     target_t = None
-    if rank == 0 and not args.no_side_legs and args.workload != "T":
+    if rank == 0 and side_legs and args.workload != "T":
         try:
             t_rt = rule_table_from_policies(policies_from_docs(workloads.t_policies()))
             t_lt = lower_rule_table(t_rt)
@@ -516,7 +530,7 @@ def main():
             t_table.synchronize()
             t_alone_ms, _ = t_table.kernel_time_ms()
             checked = None
-            if not args.no_cpu_baseline:
+            if cpu_baseline:
                 from oracle import ccheck
                 want_t = ccheck.check(t_lt, t_host[0], now, FLAGS, threads=min(32, os.cpu_count() or 1))
                 for name in ("effect", "policy", "scope"):
@@ -553,7 +567,7 @@ def main():
         capi.init(local_rank)
 
     first_checked = None
-    if rank == 0 and args.no_cpu_baseline and args.check_first:
+    if rank == 0 and args.check_first and not cpu_baseline:
         from oracle import ccheck
         try:
             want_c = ccheck.check(lt, batch0, now, FLAGS, threads=min(32, os.cpu_count() or 1))
@@ -564,7 +578,7 @@ def main():
         except ccheck.Unsupported:
             first_checked = "table outside oracle/ccheck.cpp"
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and cpu_baseline:
         # the oracle = checker + reported CPU baseline ("port": restatements, not the Go binary)
         #  * oracle/ccheck.cpp (scalar C++ restatement of check.go, -O2) over the WHOLE first batch: every
         #    output of every tuple must equal the GPU's; timed on 1 thread (repeated passes, ~10 s)
@@ -646,7 +660,7 @@ def main():
             "unit": "decisions/s",
             "value_is": "resident_decisions_per_s: whole-job rate with the inputs resident in HBM when the timed region starts (the "
                         "measurement contract of this tier: the PCIe-inclusive rate is never `value`); SURVEY.md 8(d) metric (1) - "
-                        "cbh_check_batch including H2D / D2H at batch = 1M - is `pcie_inclusive_decisions_per_s` of this same line",
+                        "cbh_check_batch including H2D / D2H at batch = 1M - is `pcie_inclusive_decisions_per_s` of this same line under --full",
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,

@@ -1,7 +1,7 @@
 """Developer aid: bench.py's control flow against the simulator build of the library (torch.cuda patched away).  Figures are meaningless;
 what it shows is that the script runs end to end and prints its line.
-    CBH_BENCH_NO_DIST=1 python tools/bench_on_sim.py --requests 3000 --batches 2 --steps 2 --warmup 1 --cpu-sample 2000 [--audit-trail]
-(the side legs keep sizes of their own - minutes on the simulator; --no-side-legs for a quick look)"""
+    CBH_BENCH_NO_DIST=1 python tools/bench_on_sim.py --requests 3000 --batches 2 --steps 2 --warmup 1 [--full --cpu-sample 2000] [--audit-trail]
+(under --full the side legs keep sizes of their own - minutes on the simulator; --full --no-side-legs for a quick look)"""
 import runpy, sys
 import os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -5,8 +5,8 @@
 #      and rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE, one pass each               -> pmc_W/
 #   2. counter calibration on known byte counts (tools/pmc_calib.hip)                          -> pmc_calibration.json
 #   3. tools/pmc_summary.py -> pmc_traffic.json, copied to profiles/r03_pmc_traffic.json ON THE BOX (what bench.py reads)
-#   4. python bench.py (driver flags: --steps 20 --warmup 3, CPU baseline + side legs)         -> bench_C2.json
-#      python bench.py --workload C3|C4|C5|T --steps 10 --warmup 2                              -> bench_W.json
+#   4. python bench.py --full (driver flags: --steps 20 --warmup 3, CPU baseline + side legs)  -> bench_C2.json
+#      python bench.py --workload C3|C4|C5|T --steps 10 --warmup 2 --full                       -> bench_W.json
 # Everything lands in gpurun_out/<tag>/ ; copy what should be judged into profiles/.
 set -u
 TAG=${1:-r03f}
@@ -34,11 +34,11 @@ for c in FETCH_SIZE WRITE_SIZE; do
 done
 python tools/pmc_summary.py $OUT > /dev/null
 cp $OUT/pmc_traffic.json profiles/r03_pmc_traffic.json
-(timeout 900 python bench.py --steps 20 --warmup 3 2>$OUT/bench_C2.err | grep '^{' | tail -1) > $OUT/bench_C2.json
+(timeout 900 python bench.py --steps 20 --warmup 3 --full 2>$OUT/bench_C2.err | grep '^{' | tail -1) > $OUT/bench_C2.json
 cut -c1-330 $OUT/bench_C2.json; echo
 for w in $WL; do
   [ $w = C2 ] && continue
-  (timeout 600 python bench.py --workload $w --steps 10 --warmup 2 2>$OUT/bench_$w.err | grep '^{' | tail -1) > $OUT/bench_$w.json
+  (timeout 600 python bench.py --workload $w --steps 10 --warmup 2 --full 2>$OUT/bench_$w.err | grep '^{' | tail -1) > $OUT/bench_$w.json
   python -c "
 import json; d=json.load(open('$OUT/bench_$w.json')); r=d['roofline']; print('$w', '%.3g dec/s' % d['value'], r['kernel'], '%.1f us' % (r['kernel_ms']*1e3), 'frac %.3f' % r['frac'], 'traffic', r['traffic'])"
 done

@@ -31,10 +31,10 @@ for c in FETCH_SIZE WRITE_SIZE; do
   ( cd /tmp && timeout -k 5 120 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/pmc_calib/$c -o $c -- /tmp/pmc_calib > $OUT/pmc_calib_$c.log 2>&1 )
 done
 python tools/pmc_summary.py $OUT | tail -1 | cut -c1-400
-(timeout -k 5 600 python bench.py --steps 20 --warmup 3 2>$OUT/bench_C2.err | grep '^{' | tail -1) > $OUT/bench_C2.json
+(timeout -k 5 600 python bench.py --steps 20 --warmup 3 --full 2>$OUT/bench_C2.err | grep '^{' | tail -1) > $OUT/bench_C2.json
 cut -c1-330 $OUT/bench_C2.json; echo
 for w in C3 C4 C5 T C5W; do
-  (timeout -k 5 400 python bench.py --workload $w --steps 10 --warmup 2 --no-cpu-baseline 2>$OUT/bench_$w.err | grep '^{' | tail -1) > $OUT/bench_$w.json
+  (timeout -k 5 400 python bench.py --workload $w --steps 10 --warmup 2 --full --no-cpu-baseline 2>$OUT/bench_$w.err | grep '^{' | tail -1) > $OUT/bench_$w.json
   python -c "
 import json; d=json.load(open('$OUT/bench_$w.json')); r=d['roofline']; s=r.get('serial') or {}
 print('$w', '%.4g dec/s' % d['value'], r['kernel'], '%.1f us' % (r['kernel_ms']*1e3), 'frac %.3f' % r['frac'], 'by itself %.1f us' % (s.get('kernel_ms', 0) * 1e3), 'traffic', r['traffic'])"

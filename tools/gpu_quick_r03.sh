@@ -9,7 +9,7 @@ if [ -z "$NOTESTS" ]; then
   timeout 900 python -m pytest tests -m gpu -x -q > $OUT/pytest_gpu.log 2>&1; echo "pytest rc $?"; tail -3 $OUT/pytest_gpu.log
 fi
 for w in $WL; do
-  (timeout 600 python bench.py --workload $w --steps 10 --warmup 2 --no-cpu-baseline 2>$OUT/bench_$w.err | grep '^{' | tail -1) > $OUT/bench_$w.json
+  (timeout 600 python bench.py --workload $w --steps 10 --warmup 2 --full --no-cpu-baseline 2>$OUT/bench_$w.err | grep '^{' | tail -1) > $OUT/bench_$w.json
   python - <<P
 import json
 try:

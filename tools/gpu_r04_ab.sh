@@ -8,7 +8,7 @@ python __graft_entry__.py > $OUT/build.log 2>&1 || { tail -20 $OUT/build.log; ex
 for w in $WL; do
   for mode in base switch; do
     if [ $mode = switch ]; then export "$SW"; else unset "${SW%%=*}"; fi
-    timeout 600 python bench.py --workload $w --steps 10 --warmup 2 --no-cpu-baseline "$@" > $OUT/bench_${w}_$mode.json 2> $OUT/bench_${w}_$mode.err
+    timeout 600 python bench.py --workload $w --steps 10 --warmup 2 --full --no-cpu-baseline "$@" > $OUT/bench_${w}_$mode.json 2> $OUT/bench_${w}_$mode.err
     python - <<P
 import json
 try:

@@ -17,7 +17,7 @@ for mode in wide general; do
   DB=$(find $OUT/prof_C5W_$mode -name '*.db' | head -1)
   [ -n "$DB" ] && python tools/rocpd_summary.py "$DB" $OUT/kernel_stats_C5W_$mode.txt | sed -n 3,8p
   rm -rf $OUT/prof_C5W_$mode
-  (timeout 600 python bench.py --workload C5W --steps 10 --warmup 2 --no-cpu-baseline 2>$OUT/bench_C5W_$mode.err | grep '^{' | tail -1) > $OUT/bench_C5W_$mode.json
+  (timeout 600 python bench.py --workload C5W --steps 10 --warmup 2 --full --no-cpu-baseline 2>$OUT/bench_C5W_$mode.err | grep '^{' | tail -1) > $OUT/bench_C5W_$mode.json
   python - <<P
 import json
 try:

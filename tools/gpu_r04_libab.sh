@@ -10,7 +10,7 @@ for rep in 1 2; do
 for w in $WL; do
   for mode in base alt; do
     [ $mode = alt ] && cp $ALT cerbos_amd/libcerbos_hip.so || cp /tmp/lib_orig.so cerbos_amd/libcerbos_hip.so
-    timeout 600 python bench.py --workload $w --steps 10 --warmup 2 --no-cpu-baseline "$@" > $OUT/bench_${w}_$mode.json 2> $OUT/bench_${w}_$mode.err
+    timeout 600 python bench.py --workload $w --steps 10 --warmup 2 --full --no-cpu-baseline "$@" > $OUT/bench_${w}_$mode.json 2> $OUT/bench_${w}_$mode.err
     python - <<P
 import json
 try:

@@ -12,7 +12,7 @@ tools/gpu_final_r04.sh $TAG
 # 4. the pre-pass in two kernels against the fused one
 for mode in 0 1; do
   for w in C5 C5W; do
-    CBH_PRE_SPLIT=$mode CBH_BENCH_NO_DIST=1 timeout 600 python bench.py --workload $w --steps 10 --warmup 2 --no-cpu-baseline > $OUT/bench_${w}_presplit$mode.json 2> $OUT/bench_${w}_presplit$mode.err
+    CBH_PRE_SPLIT=$mode CBH_BENCH_NO_DIST=1 timeout 600 python bench.py --workload $w --steps 10 --warmup 2 --full --no-cpu-baseline > $OUT/bench_${w}_presplit$mode.json 2> $OUT/bench_${w}_presplit$mode.err
     python -c "
 import json; d=json.load(open('$OUT/bench_${w}_presplit$mode.json')); r=d['roofline']; s=r.get('serial') or {}
 print('$w CBH_PRE_SPLIT=$mode', '%.3g dec/s' % d['value'], r['kernel'], 'frac %.3f' % r['frac'], 'by itself %.1f us' % (s.get('kernel_ms', 0) * 1e3))"
@@ -24,7 +24,7 @@ for w in C2 C5; do
 done
 # 5. what decision logs cost: the trail forms of the kernels, resident (bench.py --audit-trail), against the lines of step 2
 for w in C2 C3 T C5 C5W; do
-  CBH_BENCH_NO_DIST=1 timeout 600 python bench.py --workload $w --steps 10 --warmup 2 --no-cpu-baseline --audit-trail > $OUT/bench_${w}_trail.json 2> $OUT/bench_${w}_trail.err
+  CBH_BENCH_NO_DIST=1 timeout 600 python bench.py --workload $w --steps 10 --warmup 2 --full --no-cpu-baseline --audit-trail > $OUT/bench_${w}_trail.json 2> $OUT/bench_${w}_trail.err
   python -c "
 import json; d=json.load(open('$OUT/bench_${w}_trail.json')); r=d['roofline']; s=r.get('serial') or {}
 print('$w with the audit trail', '%.3g dec/s' % d['value'], r['kernel'], 'frac %.3f' % r['frac'], 'by itself %.1f us' % (s.get('kernel_ms', 0) * 1e3))"

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Round 6: a quick look at the shipped build - some GPU-tier files, then the default bench line.   usage: gpu_r06_quick.sh TAG "pytest args" [bench args]
 set -u
-TAG=${1:-r06q}; PT=${2:-""}; BA=${3:-"--steps 20 --warmup 3"}
+TAG=${1:-r06q}; PT=${2:-""}; BA=${3:-"--steps 20 --warmup 3 --full"}
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$R/gpurun_out/$TAG; mkdir -p $OUT; cd $R; export TMPDIR=/tmp
 if [ -n "$PT" ]; then (time timeout -k 5 900 python -m pytest $PT -m gpu -q -x) > $OUT/pytest.log 2>&1; echo "pytest rc $?"; tail -4 $OUT/pytest.log; fi
