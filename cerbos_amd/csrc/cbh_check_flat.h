@@ -1058,12 +1058,26 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c) {
   }
 #endif
   const bool packed = valid && act_cnt == 4 && (act_off & 3u) == 0;
-  if (packed) {
 #ifndef CBH_HOSTSIM
-    typedef u32 u32x4 __attribute__((ext_vector_type(4)));
+  typedef u32 u32x4 __attribute__((ext_vector_type(4)));
 #else
-    struct u32x4 { u32 x, y, z, w; };
+  struct u32x4 { u32 x, y, z, w; };
 #endif
+  if (flags & CBH_FI_PACKED_RES) {   // the packed form (cbh_vm.h cbh_pk_word) in the policy array: one 16-byte store per request
+    const u32 pkb = cbh_pk_bits(t.n_scopes);
+    u32 pw[4];
+#pragma unroll
+    for (u32 k = 0; k < 4; ++k) pw[k] = cbh_pk_word((eff4 >> (8 * k)) & 0xFFu, (st4 >> (8 * k)) & 0xFFu, pol[k], scp[k], pkb);
+    if (packed) {
+      if (o.edr) store_nt(o.edr + req, edr);
+      u32x4 v; v.x = pw[0]; v.y = pw[1]; v.z = pw[2]; v.w = pw[3];
+      store_nt((CBH_G u32x4*)(o.policy + act_off), v);
+    } else if (valid) {
+      if (o.edr) o.edr[req] = edr;
+#pragma unroll
+      for (u32 k = 0; k < 4; ++k) if (k < act_cnt) o.policy[act_off + k] = pw[k];
+    }
+  } else if (packed) {
     if (o.edr) store_nt(o.edr + req, edr);
     store_nt((CBH_G u32*)(o.effect + act_off), eff4);
     if (o.status) store_nt((CBH_G u32*)(o.status + act_off), st4);
@@ -1136,6 +1150,16 @@ CBH_FLAT_TRAIL_KERNEL(cbh_check_flat_trail_kernel_staged, 5, false, 1)
 CBH_FLAT_TRAIL_KERNEL(cbh_check_flat_trail_kernel_any_staged, 3, true, 1)
 CBH_FLAT_TRAIL_KERNEL(cbh_check_flat_trail_kernel_masks, 3, false, 2)
 CBH_FLAT_TRAIL_KERNEL(cbh_check_flat_trail_kernel_any_masks, 3, true, 2)
+// the packed results of a flat launch (CBH_FI_PACKED_RES, in the policy array) back into the wide form, before cbh_result_download
+// copies it
+struct PkUnpackArgs { CBH_G u8* effect; CBH_G u8* status; CBH_G u32* policy; CBH_G u32* scope; u32 n; u32 bits; };
+__global__ __launch_bounds__(256) void cbh_unpack_results_kernel(PkUnpackArgs a) {
+  const u32 i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= a.n) return;
+  const u32 w = a.policy[i];
+  a.effect[i] = (u8)cbh_pk_effect(w); a.status[i] = (u8)cbh_pk_status(w);
+  a.policy[i] = cbh_pk_policy(w, a.bits); a.scope[i] = cbh_pk_scope(w, a.bits);
+}
 #define CBH_FLAT_STAGE_MIN 32u
 // the mask walk decides a table that has segments and long buckets (CBH_FLAT_MASKS=0: never, =1: whatever the buckets' length - tests, A/B)
 static inline bool cbh_flat_use_masks(const void* segs, u32 max_bucket) {

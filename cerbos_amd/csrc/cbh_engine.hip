@@ -226,6 +226,9 @@ struct cbh_device_batch {
   u32 trail_groups = 0; u32* trail_grp = nullptr;   // cbh_batch_set_trail: groups of out.eff_pol, the requests' groups
   const u32* w_inv = nullptr;         // grouped by route: input -> position of its per-request results; else null
   u64* w_edr_input = nullptr;         // scratch of cbh_result_download: the derived-role masks back in input order
+  // Which form the last cbh_check_resident wrote: packed - out.policy holds the results as packed words (cbh_vm.h cbh_pk_word), the
+  // other three arrays are stale until cbh_result_download unpacks them; edr_zero - no derived-role mask was written, every one is 0.
+  bool res_packed = false; bool edr_zero = false;
   const u64* w_moff = nullptr; u32 w_dver_off = 0, w_dver_len = 0;   // (the device assembler reads the messages again)
   bool w_total_known = false; uint64_t w_total = 0; uint32_t w_out_errors = 0;   // cbh_wire_outputs ran its size / scan launches for this batch's current results
   u32* w_sizes = nullptr; u64* w_wavesum = nullptr; u64* w_waveoff = nullptr; WireOutStats* w_ostats = nullptr; u64* w_out_off = nullptr; u8* w_out_flags = nullptr;
@@ -649,7 +652,7 @@ static void launch_plan(const CbhPlan& pl, const TableDev& dev, KernelArgs ka, c
                         size_t pad, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr) {
   if (hi <= lo) return;
   ka.b.req_lo = lo; ka.b.req_hi = hi;
-  ka.flags &= ~(u32)CBH_FI_MASK;
+  ka.flags &= ~(u32)(CBH_FI_MASK & ~CBH_FI_PACKED_RES);   // (the result form is the caller's choice: cbh_check_resident)
   const u32 n = hi - lo;
   // (timed launches: the start event rides on the first kernel of the plan, the stop event on the last - the figure is the
   // whole plan's, gaps between its kernels included)
@@ -711,6 +714,13 @@ static size_t check_lds_bytes(const BatchDev& d, u32 table_flags) {   // the col
   return (size_t)CBH_CC_DWORDS(ncc, false) * 4 + ((table_flags & CBH_MF_NEEDS_ARENA) ? (size_t)CBH_ARENA_ENTRIES * CBH_BLOCK * 9 : 0);
 }
 
+// Can the flat kernels' results of this table take the packed form (cbh_vm.h cbh_pk_word)?  Its ids and scope indices must fit the
+// word's fields.  CBH_PACKED_RESULTS=0 (measurement aid): never.
+static bool pk_fits(const TableDev& dev) {
+  static const bool off = [] { const char* e = getenv("CBH_PACKED_RESULTS"); return e && atoi(e) == 0; }();
+  return !off && cbh_pk_bits(dev.n_scopes) <= CBH_PK_MAX_BITS;
+}
+
 extern "C" int cbh_check_resident(cbh_table* t, cbh_device_batch* b, const cbh_params* p) {
   if (!t || !b || !p) return fail("null argument");
   if (b->table != t) return fail("batch was uploaded for a different table");
@@ -739,12 +749,19 @@ extern "C" int cbh_check_resident(cbh_table* t, cbh_device_batch* b, const cbh_p
   Replica::Slot& sl = timed ? rep->ring[rep->next_slot++ % Replica::RING] : scratch_slot;
   if (timed && sl.pending) { HIPCHK(hipEventSynchronize(sl.ev[3])); collect_slot(rep, sl); }
   const BatchDev& d = b->dev;
+  const CbhPlan pl = d.n_requests ? plan_for(rep->dev, b->max_actions, b->max_roles, b->plain_tags, p->flags) : CbhPlan{};
+  // A flat launch writes its results packed, a word per tuple, where the table's ids fit (not: the trail's kernels, the wire road's
+  // batches - cbh_wire_outputs reads the wide arrays -, cycle-count launches); and for a table without derived roles no mask at all.
+  b->res_packed = pl.kind == 1 && !cbh_is_flat_trail_kernel(pl.kernel) && !b->wire && !(p->flags & CBH_F_DEBUG_CYCLES) && pk_fits(rep->dev);
+  b->edr_zero = b->res_packed && rep->dev.n_dr == 0;
   {
     // launch arguments live in device memory; re-sent only when they change (the kernel itself
     // writes every output word of every request, so nothing needs clearing between launches)
     KernelArgs ka;
     std::memset(&ka, 0, sizeof(ka));
     ka.t = rep->dev; ka.b = d; ka.o = b->out; ka.now_ns = p->now_ns; ka.flags = p->flags & ~(u32)CBH_FI_MASK;
+    if (b->res_packed) ka.flags |= CBH_FI_PACKED_RES;
+    if (b->edr_zero) ka.o.edr = nullptr;
     if (!b->have_args || std::memcmp(&ka, &b->last_args, sizeof(ka)) != 0) {
       b->last_args = ka; b->have_args = true;
       HIPCHK(hipMemcpyAsync(b->d_args, &b->last_args, sizeof(ka), hipMemcpyHostToDevice, s));
@@ -762,7 +779,6 @@ extern "C" int cbh_check_resident(cbh_table* t, cbh_device_batch* b, const cbh_p
   }
   sl.pending = false;
   if (d.n_requests) {
-    const CbhPlan pl = plan_for(rep->dev, b->max_actions, b->max_roles, b->plain_tags, p->flags);
     launch_plan(pl, rep->dev, b->last_args, (const KernelArgs*)b->d_args, 0, d.n_requests, b->wide_lo, b->wide_hi, lds_pad(), s, timed ? sl.ev[2] : nullptr, timed ? sl.ev[3] : nullptr);
     sl.pending = timed;
   }
@@ -840,11 +856,19 @@ extern "C" int cbh_result_download(cbh_table* t, cbh_device_batch* b, cbh_result
   HIPCHK(hipSetDevice(rep->device));
   hipStream_t s = b->stream;
   const BatchDev& d = b->dev;
+  if (b->res_packed && d.n_tuples) {   // the last launch wrote the packed form: unpacked into the wide arrays, which then cross as before
+    PkUnpackArgs ua; ua.effect = b->out.effect; ua.status = b->out.status; ua.policy = b->out.policy; ua.scope = b->out.scope;
+    ua.n = d.n_tuples; ua.bits = cbh_pk_bits(rep->dev.n_scopes);
+    hipLaunchKernelGGL(cbh_unpack_results_kernel, dim3((d.n_tuples + 255u) / 256u), dim3(256), 0, s, ua);
+    HIPCHK(hipGetLastError());
+    b->res_packed = false;   // (in place: the wide form is the live one now)
+  }
   if (d.n_tuples) HIPCHK(hipMemcpyAsync(out->effect, b->out.effect, d.n_tuples, hipMemcpyDeviceToHost, s));
   if (out->policy && d.n_tuples) HIPCHK(hipMemcpyAsync(out->policy, b->out.policy, (size_t)d.n_tuples * 4, hipMemcpyDeviceToHost, s));
   if (out->scope && d.n_tuples) HIPCHK(hipMemcpyAsync(out->scope, b->out.scope, (size_t)d.n_tuples * 4, hipMemcpyDeviceToHost, s));
   if (out->status && d.n_tuples) HIPCHK(hipMemcpyAsync(out->status, b->out.status, d.n_tuples, hipMemcpyDeviceToHost, s));
-  if (out->edr_mask && d.n_requests) {
+  if (out->edr_mask && d.n_requests && b->edr_zero) std::memset(out->edr_mask, 0, (size_t)d.n_requests * 8);
+  else if (out->edr_mask && d.n_requests) {
     const u64* src = b->out.edr;
     if (b->w_inv) {   // a batch grouped by route: the masks follow their requests back to input order
       if (!b->w_edr_input && dalloc(b, b->w_edr_input, (size_t)d.n_requests) != 0) return -1;

@@ -104,6 +104,20 @@ struct OutDev {
   // the group (check.go:302-304, the AuditTrail's effective policies); null = not wanted
   CBH_G u32* eff_pol;
 };
+// The packed form of the flat kernels' results (CBH_FI_PACKED_RES): one word per tuple, written where the policy word goes
+// (OutDev.policy), instead of effect, status, policy and scope: effect (2 bits) | status (2) | policy kind (3) | policy id (B) |
+// scope + 1 (B; 0 = CBH_NONE), B = cbh_pk_bits(the table's scope count).  Lossless for the flat kernels' results: their policy
+// words are NO_MATCH / "" with id 0 or resource.<kind> with a scope index as id (cbh_check_flat.h, the fold).  A table of more
+// than 2^CBH_PK_MAX_BITS - 1 scopes keeps the wide form.
+#define CBH_PK_MAX_BITS 12u
+__host__ __device__ __forceinline__ u32 cbh_pk_bits(u32 n_scopes) { return 32u - (u32)__builtin_clz(n_scopes | 1u); }
+__device__ __forceinline__ u32 cbh_pk_word(u32 eff, u32 st, u32 pol, u32 scp, u32 B) {
+  return eff | (st << 2) | ((pol >> 28) << 4) | ((pol & 0x0FFFFFFFu) << 7) | ((scp + 1u) << (7u + B));
+}
+__device__ __forceinline__ u32 cbh_pk_effect(u32 w) { return w & 3u; }
+__device__ __forceinline__ u32 cbh_pk_status(u32 w) { return (w >> 2) & 3u; }
+__device__ __forceinline__ u32 cbh_pk_policy(u32 w, u32 B) { return ((w >> 4) & 7u) << 28 | ((w >> 7) & ((1u << B) - 1u)); }
+__device__ __forceinline__ u32 cbh_pk_scope(u32 w, u32 B) { return (w >> (7u + B)) - 1u; }   // (0 -> CBH_NONE)
 // (idempotent: a stale read costs an atomic, never a bit.  The read goes to L2 - agent scope - on purpose: a CU's L1 would keep
 // answering "not set" for the rest of the launch, and every later visit of every wave of that CU would queue an atomic on the one word)
 __device__ __forceinline__ void ep_mark(const OutDev& o, const BatchDev& b, u32 req, u32 policy) {
@@ -129,7 +143,8 @@ struct __attribute__((aligned(16))) KernelArgs { TableDev t; BatchDev b; OutDev 
 #define CBH_FI_ONLY_WIDE 0x20000u   /* cbh_check_kernel*: only the requests wider than the base shape are this launch's */
 #define CBH_FI_ONLY_WIDER 0x40000u  /* cbh_check_kernel*: only the requests no shape of the walk holds are this launch's */
 #define CBH_FI_PACKED_TAGS 0x80000u /* the column cache keeps a tag as a byte (CBH_CC_DWORDS): chosen per launch, where the smaller cache lets a CU hold more workgroups */
-#define CBH_FI_MASK 0xF0000u
+#define CBH_FI_PACKED_RES 0x100000u /* the flat kernels write a packed word per tuple (cbh_pk_word) into OutDev.policy, and leave effect / status / scope alone */
+#define CBH_FI_MASK 0x1F0000u
 #define CBH_W2_NA 8u
 #define CBH_W2_NR 4u
 #define CBH_W2_WIDE_NR 8u           /* the wider shapes: 8 actions x 8 roles (cbh_walk2_wide_kernel) ... */
