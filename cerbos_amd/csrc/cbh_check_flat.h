@@ -436,7 +436,8 @@ __device__ __forceinline__ u64 load_u64g(const CBH_G u32* p) {   // 8-byte align
 // (not those of a role behind the one that allowed) have touched.  A bucket of a flat table is one resource policy's.
 // MEMO: the walk keeps the wave's last four condition outcomes (leafish_memo below) - the instantiation for tables WITH derived roles
 // (cbh_check_flat_kernel_dr): the memo's registers cost the plain kernel a wave of occupancy and C2 2 % for nothing.
-template <bool WITH_CALL, int MODE, bool EP = false, bool MEMO = false>
+// COMPACT: the request record and the 32-bit value planes of a resident batch (cbh_vm.h BatchDev.creq / cval) instead of the wide arrays.
+template <bool WITH_CALL, int MODE, bool EP = false, bool MEMO = false, bool COMPACT = false>
 __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c) {
   constexpr bool STAGED = MODE == 1;
   constexpr u32 BTYPE = MODE == 2 ? (u32)CBH_B_RESSEG : (u32)CBH_B_RESOURCE;
@@ -458,10 +459,34 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c) {
   const bool valid = rix < b.req_hi;
   const u32 req = valid ? rix : b.req_lo;
   const u32 NR = b.n_requests;
+  const u32 w0r = b.req_lo + blockIdx.x * CBH_FLAT_THREADS + wave * CBH_BLOCK;
+  const u32 w0 = w0r < b.req_hi ? w0r : b.req_lo;   // the wave's first request (uniform): the columns' planes are addressed from it
+  const u32 wd = valid ? c.tid : 0u;                // ... and this lane's distance from it
+  const u32 kmax = t.K ? t.K - 1u : 0u;
+  u32 pid, kind, r_scope, r_ver, role_off = 0, act_off, role_cnt, act_cnt;
+  u32 ac[4], rc[4];
+  u32x4u sp{0, 0, 0, 0};
+  u32 cls_a0 = 0, cls_r0 = 0;
+  bool spec = false; u32 spec_ix = 0;
+  if constexpr (COMPACT) {
+    // ---- the compact form (cbh_vm.h BatchDev.creq): ONE 16-byte load brings everything the walk takes from the request words, the
+    // role ids and the action ids - the classes were looked up when the batch was uploaded.  First trip: the record and the tag
+    // bytes; second: the columns' copies and the chain's first scope.  No class table is read, none is staged in LDS, and the
+    // prologue has no barrier of its own.
+    const u32x4u rec = load_u32x4(b.creq + 4u * (size_t)req);
+    pid = rec.x; kind = rec.y & 0xFFFFu; r_ver = rec.y >> 16;
+    const u32 w2 = valid ? rec.z : ((rec.z & 0xFFFFu) | 0xFFC00000u), w3 = valid ? rec.w : (rec.w | 0x3FFFFFFFu);   // (a lane beyond the batch's end: no action, no role)
+    r_scope = (w2 & 0xFFFFu) | (w3 & CBH_SCOPE_EXACT);
+    role_cnt = (w2 >> 16) & 7u; act_cnt = (w2 >> 19) & 7u;   // both <= 4
+#pragma unroll
+    for (u32 k = 0; k < 4; ++k) ac[k] = (w3 >> (5u * k)) & 31u;
+    rc[0] = (w3 >> 20) & 31u; rc[1] = (w3 >> 25) & 31u; rc[2] = (w2 >> 22) & 31u; rc[3] = w2 >> 27;
+    act_off = 4u * req;   // (a batch of four-action requests laid out back to back; any other reads the request word where the results are stored)
+  } else {
 #define RQ(f) b.req_u32[(size_t)(f) * NR + req]
-  const u32 pid = RQ(CBH_RQ_PRINCIPAL_ID), kind = RQ(CBH_RQ_KIND), r_scope = RQ(CBH_RQ_R_SCOPE), r_ver = RQ(CBH_RQ_R_VERSION);
-  const u32 role_off = RQ(CBH_RQ_ROLE_OFF), act_off = RQ(CBH_RQ_ACT_OFF);
-  const u32 role_cnt = valid ? RQ(CBH_RQ_ROLE_CNT) : 0, act_cnt = valid ? RQ(CBH_RQ_ACT_CNT) : 0;   // both <= 4 (host-checked)
+  pid = RQ(CBH_RQ_PRINCIPAL_ID); kind = RQ(CBH_RQ_KIND); r_scope = RQ(CBH_RQ_R_SCOPE); r_ver = RQ(CBH_RQ_R_VERSION);
+  role_off = RQ(CBH_RQ_ROLE_OFF); act_off = RQ(CBH_RQ_ACT_OFF);
+  role_cnt = valid ? RQ(CBH_RQ_ROLE_CNT) : 0; act_cnt = valid ? RQ(CBH_RQ_ACT_CNT) : 0;   // both <= 4 (host-checked)
 #undef RQ
   // ---- the request's loads, in TWO round trips to memory.  First trip, all issued back to back and depending on nothing: the
   // request words above, the four action ids (speculated, below), this thread's bytes of the two class tables, the tag bytes of
@@ -470,18 +495,15 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c) {
   // their destinations waits for all of them - behind this prologue's own LDS stores.  (They used to go out first: the class
   // tables' LDS stores then waited for the columns, the action ids were loaded behind that wait and the role ids behind another
   // - three trips, and one more per column where the tags are packed.)
-  const u32 w0r = b.req_lo + blockIdx.x * CBH_FLAT_THREADS + wave * CBH_BLOCK;
-  const u32 w0 = w0r < b.req_hi ? w0r : b.req_lo;   // the wave's first request (uniform): the columns' planes are addressed from it
-  const u32 wd = valid ? c.tid : 0u;                // ... and this lane's distance from it
   // Actions: a batch of four-action requests laid out back to back has ACT_OFF = 4 * request - read the four ids from
   // there with ONE 16-byte load that does not wait for ACT_OFF to arrive, and fall back to the dependent loads for the
   // lanes where the guess was wrong.  (Unconditional: without four tuples the load reads request words and is not used.)
-  const bool spec = b.n_tuples >= 4u;   // wave-uniform
-  const u32 spec_ix = (4u * req + 4u <= b.n_tuples) ? 4u * req : 0u;
-  const u32x4u sp = load_u32x4(spec ? b.tuple_action + spec_ix : b.req_u32);
-  const u32 kmax = t.K ? t.K - 1u : 0u;
+  spec = b.n_tuples >= 4u;   // wave-uniform
+  spec_ix = (4u * req + 4u <= b.n_tuples) ? 4u * req : 0u;
+  sp = load_u32x4(spec ? b.tuple_action + spec_ix : b.req_u32);
   const u32 cls_i = threadIdx.x < t.K ? threadIdx.x : kmax;
-  const u32 cls_a0 = (t.K ? t.action_class : (const CBH_G u8*)b.req_u32)[cls_i], cls_r0 = (t.K ? t.role_class : (const CBH_G u8*)b.req_u32)[cls_i];
+  cls_a0 = (t.K ? t.action_class : (const CBH_G u8*)b.req_u32)[cls_i]; cls_r0 = (t.K ? t.role_class : (const CBH_G u8*)b.req_u32)[cls_i];
+  }
   const CcTags cct = cc_load_tags(c, b, NR, w0, wd);
   const u32 all = (1u << act_cnt) - 1u;
   // [depth][lane]: scope index at that depth of the lane's chain - in the dynamic LDS behind the column caches,
@@ -502,8 +524,9 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c) {
   // dependent trip to memory.
   const bool cls_in_lds = t.K <= CBH_FLAT_LDS_STRINGS;
   CBH_L u8* cls_lds = (CBH_L u8*)((CBH_L u32*)cbh_dyn_lds + CBH_FLAT_WAVES * (CBH_CC_DWORDS(c.n_cached, (c.flags & CBH_FI_PACKED_TAGS) != 0) + chain_dwords));   // [action classes K][role classes K]
-  // second trip: the role ids (and, where the speculation missed, the action ids)
-  u32 ac[4], rc[4], aid[4], rid[4];
+  // second trip (wide form): the role ids (and, where the speculation missed, the action ids)
+  u32 aid[4] = {0, 0, 0, 0}, rid[4] = {0, 0, 0, 0};
+  if constexpr (!COMPACT) {
 #pragma unroll
   for (u32 k = 0; k < 4; ++k) rid[k] = b.roles[k < role_cnt ? role_off + k : 0u];
   const bool spec_hit = spec && act_cnt == 4u && act_off == spec_ix;
@@ -516,6 +539,7 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c) {
     if (threadIdx.x < t.K) { cls_lds[threadIdx.x] = (u8)cls_a0; cls_lds[t.K + threadIdx.x] = (u8)cls_r0; }
     for (u32 i = threadIdx.x + CBH_FLAT_THREADS; i < t.K; i += CBH_FLAT_THREADS) { cls_lds[i] = t.action_class[i]; cls_lds[t.K + i] = t.role_class[i]; }
   }
+  }
   // MODE 2: the class masks of the segment being decided, per wave (behind the class tables: cbh_flat_class_bytes is a multiple of 16)
   CBH_L u64* segm = (CBH_L u64*)(cls_lds + (cls_in_lds ? ((2u * t.K + 15u) & ~15u) : 0u)) + wave * (CBH_SEG_LDS_BYTES / 8u);
   CBH_L u8* seg_rec = (CBH_L u8*)(segm + 64);      // [2][64]: record -> item of its condition / of its derived-role condition
@@ -525,11 +549,12 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c) {
   CBH_L u32* ep_lds = (CBH_L u32*)(cls_lds + (cls_in_lds ? ((2u * t.K + 15u) & ~15u) : 0u) + (MODE == 2 ? CBH_FLAT_WAVES * CBH_SEG_LDS_BYTES : 0u)) + wave * max_depth * 2u * CBH_BLOCK;
   const bool want_ep = EP && (flags & CBH_F_WANT_EFFECTIVE_POLICIES) != 0 && o.eff_pol != nullptr;
   if (EP) { for (u32 d = 0; d < 2u * max_depth; ++d) ep_lds[d * CBH_BLOCK + c.tid] = 0; }
-  cc_fill(c, b, NR, w0, wd, cct);   // (behind every LDS store of this prologue)
+  if constexpr (COMPACT) cc_fill_compact(c, b, NR, w0, wd, cct); else cc_fill(c, b, NR, w0, wd, cct);   // (behind every LDS store of this prologue)
   // ... and the chain's first scope (ruletable.go:848-882; per lane, reads the scope tables): its load goes out with the second trip
   const bool lenient = (flags & CBH_F_LENIENT_SCOPE_SEARCH) != 0;
   const u32 first = chain_first(t, r_scope, FLAG_RES, lenient);
-  if (cls_in_lds) {
+  if constexpr (COMPACT) {
+  } else if (cls_in_lds) {
     __syncthreads();
 #pragma unroll
     for (u32 k = 0; k < 4; ++k) {
@@ -1057,6 +1082,8 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c) {
     scp[0] = (u32)rt0; scp[1] = (u32)__builtin_amdgcn_s_memrealtime(); scp[2] = dbg_rows | (dbg_evals << 16); scp[3] = dbg_rounds | (dbg_visits << 16);
   }
 #endif
+  // (compact form: only the stores need the offset - a load up here, inside a uniform branch, would be waited for in the prologue)
+  if constexpr (COMPACT) { if (!(b.compact_info & CBH_CI_ACT4)) act_off = b.req_u32[(size_t)CBH_RQ_ACT_OFF * NR + req]; }
   const bool packed = valid && act_cnt == 4 && (act_off & 3u) == 0;
 #ifndef CBH_HOSTSIM
   typedef u32 u32x4 __attribute__((ext_vector_type(4)));
@@ -1141,6 +1168,22 @@ __global__ CBH_FLAT_ATTRS(3) void cbh_check_flat_kernel_any_masks(const KernelAr
   CBH_FLAT_CTX(a, ka);
   flat_body<true, 2>(a, c);
 }
+// The instantiations without the evaluator call once more, for a resident batch in its compact form (CBH_FI_COMPACT; cbh_vm.h
+// BatchDev.creq / cval).  The variants with the call keep the wide form (they ignore the flag): they are bound by the call's
+// registers, not by the bytes they read.  So does cbh_check_flat_kernel_dr: at its 72 registers (seven waves) the compact prologue
+// spilled two of them to scratch, and C3 is bound by instructions.
+__global__ CBH_FLAT_ATTRS(7) void cbh_check_flat_kernel_c(const KernelArgs a, const KernelArgs* __restrict__ ka) {
+  CBH_FLAT_CTX(a, ka);
+  flat_body<false, 0, false, false, true>(a, c);
+}
+__global__ CBH_FLAT_ATTRS(5) void cbh_check_flat_kernel_staged_c(const KernelArgs a, const KernelArgs* __restrict__ ka) {
+  CBH_FLAT_CTX(a, ka);
+  flat_body<false, 1, false, false, true>(a, c);
+}
+__global__ CBH_FLAT_ATTRS(4) void cbh_check_flat_kernel_masks_c(const KernelArgs a, const KernelArgs* __restrict__ ka) {
+  CBH_FLAT_CTX(a, ka);
+  flat_body<false, 2, false, false, true>(a, c);
+}
 // cbh_check_batch_trail on a flat table: the same six walks with the effective policies kept (flat_body EP)
 #define CBH_FLAT_TRAIL_KERNEL(NAME, MINW, CALL, MODE)                                                                          \
   __global__ CBH_FLAT_ATTRS(MINW) void NAME(const KernelArgs a, const KernelArgs* __restrict__ ka) { CBH_FLAT_CTX(a, ka); flat_body<CALL, MODE, true>(a, c); }
@@ -1159,6 +1202,64 @@ __global__ __launch_bounds__(256) void cbh_unpack_results_kernel(PkUnpackArgs a)
   const u32 w = a.policy[i];
   a.effect[i] = (u8)cbh_pk_effect(w); a.status[i] = (u8)cbh_pk_status(w);
   a.policy[i] = cbh_pk_policy(w, a.bits); a.scope[i] = cbh_pk_scope(w, a.bits);
+}
+// ---- the compact form of a resident batch (cbh_vm.h BatchDev.creq / cval), derived from the wide arrays on the device when the
+// batch is uploaded.  Two launches of one lane per request: the scan says which cached columns have a non-zero high word somewhere,
+// whether every field fits the record and whether the actions lie four to a request back to back; the pack writes the records
+// and the 32-bit planes.
+struct CompactArgs {
+  const CBH_G u32* req_u32; const CBH_G u32* roles; const CBH_G u32* tuple_action; const CBH_G u64* col_val;
+  const CBH_G u8* action_class; const CBH_G u8* role_class;
+  CBH_G u32* creq; CBH_G u32* cval; CBH_G u32* info;   // info[0]: bit k = column k has a high word, CBH_CI_MISFIT, CBH_CI_ACT4 INVERTED (some request is not aligned)
+  u32 n_requests, n_cached, K, narrow;
+};
+__global__ __launch_bounds__(256) void cbh_compact_scan_kernel(CompactArgs a) {
+  const u32 r = blockIdx.x * 256u + threadIdx.x;
+  if (r >= a.n_requests) return;
+  const size_t NR = a.n_requests;
+  u32 m = 0;
+  for (u32 k = 0; k < a.n_cached; ++k) m |= (u32)(a.col_val[k * NR + r] >> 32) ? 1u << k : 0u;
+#define RQ(f) a.req_u32[(size_t)(f) * NR + r]
+  if ((RQ(CBH_RQ_KIND) | RQ(CBH_RQ_R_VERSION) | (RQ(CBH_RQ_R_SCOPE) & ~CBH_SCOPE_EXACT)) >> 16) m |= CBH_CI_MISFIT;
+  if (RQ(CBH_RQ_ROLE_CNT) > 4u || RQ(CBH_RQ_ACT_CNT) > 4u) m |= CBH_CI_MISFIT;
+  if (RQ(CBH_RQ_ACT_OFF) != 4u * r || RQ(CBH_RQ_ACT_CNT) != 4u) m |= CBH_CI_ACT4;
+#undef RQ
+  // (idempotent, as ep_mark: read first - most lanes find their bits set already)
+#ifdef CBH_HOSTSIM
+  a.info[0] |= m;
+#else
+  if (m & ~__hip_atomic_load(a.info, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicOr((unsigned int*)a.info, m);
+#endif
+}
+__global__ __launch_bounds__(256) void cbh_compact_pack_kernel(CompactArgs a) {
+  const u32 r = blockIdx.x * 256u + threadIdx.x;
+  if (r >= a.n_requests) return;
+  const size_t NR = a.n_requests;
+#define RQ(f) a.req_u32[(size_t)(f) * NR + r]
+  const u32 pid = RQ(CBH_RQ_PRINCIPAL_ID), kind = RQ(CBH_RQ_KIND), r_scope = RQ(CBH_RQ_R_SCOPE), r_ver = RQ(CBH_RQ_R_VERSION);
+  const u32 role_off = RQ(CBH_RQ_ROLE_OFF), act_off = RQ(CBH_RQ_ACT_OFF), role_cnt = RQ(CBH_RQ_ROLE_CNT), act_cnt = RQ(CBH_RQ_ACT_CNT);
+#undef RQ
+  // the classes by the wide prologue's own expressions (flat_body), clamps included
+  const u32 kmax = a.K ? a.K - 1u : 0u;
+  u32 ac[4], rc[4];
+  for (u32 k = 0; k < 4; ++k) {
+    const u32 aid = a.tuple_action[k < act_cnt ? act_off + k : 0u], rid = a.roles[k < role_cnt ? role_off + k : 0u];
+    const u32 ca = a.K ? a.action_class[aid < a.K ? aid : kmax] : 31u, cr = a.K ? a.role_class[rid < a.K ? rid : kmax] : 31u;
+    ac[k] = (k < act_cnt && aid < a.K && ca < 31u) ? ca : 31u;
+    rc[k] = (k < role_cnt && rid < a.K && cr < 31u) ? cr : 31u;
+  }
+  CBH_G u32* rec = a.creq + 4u * (size_t)r;
+  rec[0] = pid; rec[1] = cbh_creq_w1(kind, r_ver);
+  rec[2] = cbh_creq_w2(r_scope, role_cnt, act_cnt, rc[2], rc[3]);
+  rec[3] = cbh_creq_w3(r_scope, ac[0], ac[1], ac[2], ac[3], rc[0], rc[1]);
+  u32 plane = 0;
+  for (u32 k = 0; k < a.n_cached; ++k)
+    if ((a.narrow >> k) & 1u) { a.cval[plane * NR + r] = (u32)a.col_val[k * NR + r]; ++plane; }
+}
+// the compact instantiation of a flat kernel, or null where it has none (the variants with the evaluator call, the derived-role variant, the trail's)
+static inline cbh_check_kernel_fn cbh_flat_compact_variant(cbh_check_kernel_fn fn) {
+  return fn == cbh_check_flat_kernel ? cbh_check_flat_kernel_c
+       : fn == cbh_check_flat_kernel_staged ? cbh_check_flat_kernel_staged_c : fn == cbh_check_flat_kernel_masks ? cbh_check_flat_kernel_masks_c : nullptr;
 }
 #define CBH_FLAT_STAGE_MIN 32u
 // the mask walk decides a table that has segments and long buckets (CBH_FLAT_MASKS=0: never, =1: whatever the buckets' length - tests, A/B)

@@ -229,6 +229,8 @@ struct cbh_device_batch {
   // Which form the last cbh_check_resident wrote: packed - out.policy holds the results as packed words (cbh_vm.h cbh_pk_word), the
   // other three arrays are stale until cbh_result_download unpacks them; edr_zero - no derived-role mask was written, every one is 0.
   bool res_packed = false; bool edr_zero = false;
+  // The batch has its compact form (cbh_vm.h BatchDev.creq / cval; batch_compact below): the flat kernels' compact instantiations read it.
+  bool compact = false;
   const u64* w_moff = nullptr; u32 w_dver_off = 0, w_dver_len = 0;   // (the device assembler reads the messages again)
   bool w_total_known = false; uint64_t w_total = 0; uint32_t w_out_errors = 0;   // cbh_wire_outputs ran its size / scan launches for this batch's current results
   u32* w_sizes = nullptr; u64* w_wavesum = nullptr; u64* w_waveoff = nullptr; WireOutStats* w_ostats = nullptr; u64* w_out_off = nullptr; u8* w_out_flags = nullptr;
@@ -548,7 +550,36 @@ static int dalloc(cbh_device_batch* b, T*& dst, size_t n) {
   return 0;
 }
 
-extern "C" int cbh_batch_upload_on(cbh_table* t, uint32_t device_index, const cbh_batch* in, cbh_device_batch** out) {
+// The compact form of a batch the flat kernels can decide (cbh_vm.h BatchDev.creq / cval), derived on the batch's stream from the wide
+// arrays already enqueued: the scan's verdict crosses to the host (one word), then the records and the 32-bit planes are written.  A
+// batch with a field that does not fit the record keeps the wide form; so does every batch under CBH_COMPACT_INPUTS=0 (measurement aid).
+static bool compact_inputs_on() { static const bool off = [] { const char* e = getenv("CBH_COMPACT_INPUTS"); return e && atoi(e) == 0; }(); return !off; }
+static int batch_compact(cbh_device_batch* b, hipStream_t s) {
+  const TableDev& dev = b->rep->dev;
+  BatchDev& d = b->dev;
+  if (!compact_inputs_on() || !(dev.flags & CBH_MF_FLAT) || b->max_actions > 4 || b->max_roles > 4 || !d.n_requests) return 0;
+  CompactArgs ca{};
+  ca.req_u32 = d.req_u32; ca.roles = d.roles; ca.tuple_action = d.tuple_action; ca.col_val = d.col_val;
+  ca.action_class = dev.action_class; ca.role_class = dev.role_class; ca.K = dev.K;
+  ca.n_requests = d.n_requests; ca.n_cached = d.n_columns < CBH_CACHE_COLS ? d.n_columns : CBH_CACHE_COLS;
+  if (dalloc(b, ca.info, 1) != 0) return -1;
+  const dim3 grid((d.n_requests + 255u) / 256u);
+  u32 info = 0;
+  HIPCHK(hipMemsetAsync(ca.info, 0, 4, s));
+  hipLaunchKernelGGL(cbh_compact_scan_kernel, grid, dim3(256), 0, s, ca);
+  HIPCHK(hipMemcpyAsync(&info, ca.info, 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (info & CBH_CI_MISFIT) return 0;
+  ca.narrow = ~info & ((1u << ca.n_cached) - 1u) & CBH_CI_NARROW_MASK;
+  if (dalloc(b, ca.creq, (size_t)4 * d.n_requests) != 0 || dalloc(b, ca.cval, (size_t)__builtin_popcount(ca.narrow) * d.n_requests) != 0) return -1;
+  hipLaunchKernelGGL(cbh_compact_pack_kernel, grid, dim3(256), 0, s, ca);
+  HIPCHK(hipGetLastError());
+  d.creq = ca.creq; d.cval = ca.cval; d.compact_info = ca.narrow | ((info & CBH_CI_ACT4) ? 0u : CBH_CI_ACT4);
+  b->compact = true;
+  return 0;
+}
+
+static int batch_upload(cbh_table* t, uint32_t device_index, const cbh_batch* in, cbh_device_batch** out, bool compact) {
   if (!t || !in || !out) return fail("null argument");
   if (device_index >= t->reps.size()) return fail("device index out of range");
   BatchShape sh;
@@ -595,10 +626,12 @@ extern "C" int cbh_batch_upload_on(cbh_table* t, uint32_t device_index, const cb
   if (in->n_strings && hipMemsetAsync(d.gbits, 0, (size_t)3 * in->n_strings * sizeof(u64), s) != hipSuccess) {
     cbh_batch_release(b); return fail("upload failed");
   }
+  if (compact && batch_compact(b, s) != 0) { cbh_batch_release(b); return -1; }
   if (hipStreamSynchronize(s) != hipSuccess) { cbh_batch_release(b); return fail("upload failed"); }
   *out = b;
   return 0;
 }
+extern "C" int cbh_batch_upload_on(cbh_table* t, uint32_t device_index, const cbh_batch* in, cbh_device_batch** out) { return batch_upload(t, device_index, in, out, true); }
 extern "C" int cbh_batch_upload(cbh_table* t, const cbh_batch* in, cbh_device_batch** out) { return cbh_batch_upload_on(t, 0, in, out); }
 
 static void collect_slot(Replica* r, Replica::Slot& sl) {   // the slot's last event has completed
@@ -652,7 +685,7 @@ static void launch_plan(const CbhPlan& pl, const TableDev& dev, KernelArgs ka, c
                         size_t pad, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr) {
   if (hi <= lo) return;
   ka.b.req_lo = lo; ka.b.req_hi = hi;
-  ka.flags &= ~(u32)(CBH_FI_MASK & ~CBH_FI_PACKED_RES);   // (the result form is the caller's choice: cbh_check_resident)
+  ka.flags &= ~(u32)(CBH_FI_MASK & ~(CBH_FI_PACKED_RES | CBH_FI_COMPACT));   // (the result form and the input form are the caller's choice: cbh_check_resident)
   const u32 n = hi - lo;
   // (timed launches: the start event rides on the first kernel of the plan, the stop event on the last - the figure is the
   // whole plan's, gaps between its kernels included)
@@ -703,7 +736,7 @@ static void launch_plan(const CbhPlan& pl, const TableDev& dev, KernelArgs ka, c
   }
   static const bool pre_only = getenv("CBH_PRE_ONLY") != nullptr;   // measurement aid (profiling build): the pre-pass alone
   if (pre_only && pl.kind == 2) return;
-  go(pl.kernel, (n + pl.threads - 1) / pl.threads, pl.threads, plan_lds(false, CBH_W2_NA, pad), ka, true);
+  go((ka.flags & CBH_FI_COMPACT) ? cbh_flat_compact_variant(pl.kernel) : pl.kernel, (n + pl.threads - 1) / pl.threads, pl.threads, plan_lds(false, CBH_W2_NA, pad), ka, true);
 }
 // CBH_LDS_PAD=<bytes> (measurement aid): extra dynamic LDS per workgroup of the resident launches, to hold the occupancy down
 static size_t lds_pad() { static const size_t pad = [] { const char* e = getenv("CBH_LDS_PAD"); return e ? (size_t)atol(e) : (size_t)0; }(); return pad; }
@@ -719,6 +752,12 @@ static size_t check_lds_bytes(const BatchDev& d, u32 table_flags) {   // the col
 static bool pk_fits(const TableDev& dev) {
   static const bool off = [] { const char* e = getenv("CBH_PACKED_RESULTS"); return e && atoi(e) == 0; }();
   return !off && cbh_pk_bits(dev.n_scopes) <= CBH_PK_MAX_BITS;
+}
+
+// Does this launch read the batch's compact form?  A flat kernel that has a compact instantiation (not: the variants with the
+// evaluator call, the trail's kernels), and not a cycle-count launch.
+static bool launch_is_compact(const cbh_device_batch* b, const CbhPlan& pl, u32 eval_flags) {
+  return b->compact && pl.kind == 1 && !(eval_flags & CBH_F_DEBUG_CYCLES) && cbh_flat_compact_variant(pl.kernel) != nullptr;
 }
 
 extern "C" int cbh_check_resident(cbh_table* t, cbh_device_batch* b, const cbh_params* p) {
@@ -761,6 +800,7 @@ extern "C" int cbh_check_resident(cbh_table* t, cbh_device_batch* b, const cbh_p
     std::memset(&ka, 0, sizeof(ka));
     ka.t = rep->dev; ka.b = d; ka.o = b->out; ka.now_ns = p->now_ns; ka.flags = p->flags & ~(u32)CBH_FI_MASK;
     if (b->res_packed) ka.flags |= CBH_FI_PACKED_RES;
+    if (launch_is_compact(b, pl, p->flags)) ka.flags |= CBH_FI_COMPACT;
     if (b->edr_zero) ka.o.edr = nullptr;
     if (!b->have_args || std::memcmp(&ka, &b->last_args, sizeof(ka)) != 0) {
       b->last_args = ka; b->have_args = true;
@@ -819,6 +859,7 @@ extern "C" const char* cbh_plan_describe(cbh_table* t, cbh_device_batch* b, cons
                            : pl.kernel == cbh_check_flat_kernel_staged ? "cbh_check_flat_kernel_staged" : pl.kernel == cbh_check_flat_kernel_masks ? "cbh_check_flat_kernel_masks"
                            : pl.kernel == cbh_check_flat_kernel_any_masks ? "cbh_check_flat_kernel_any_masks" : "cbh_check_flat_kernel_any_staged";
   else s = "cbh_check_kernel*";
+  if (launch_is_compact(b, pl, p->flags)) { char m[64]; snprintf(m, sizeof m, "[compact inputs, narrow columns 0x%x]", b->dev.compact_info & CBH_CI_NARROW_MASK); s += m; }
   return s.c_str();
 }
 
@@ -937,7 +978,7 @@ extern "C" int cbh_check_batch_trail(cbh_table* t, const cbh_batch* in, const cb
                                      uint32_t n_groups, uint32_t* effective_policies) {
   if (!t || !in || !p || !out || !effective_policies) return fail("null argument");
   cbh_device_batch* b = nullptr;
-  if (cbh_batch_upload_on(t, 0, in, &b) != 0) return -1;
+  if (batch_upload(t, 0, in, &b, false) != 0) return -1;   // (a trail launch reads the wide arrays)
   struct Release { cbh_device_batch* b; ~Release() { cbh_batch_release(b); } } release{b};
   if (cbh_batch_set_trail(t, b, group_of_request, n_groups) != 0) return -1;
   cbh_params q = *p;

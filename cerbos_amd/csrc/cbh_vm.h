@@ -94,8 +94,33 @@ struct BatchDev {
   u32 n_gwords; u32 n_gslots;   // words per request; sites filed = slots 0 .. n_gslots - 1
   const CBH_G u32* ep_group;    // cbh_check_batch_trail: the group (Check call) request i belongs to, or null (one group)
   // the split pre-pass (cbh_walk2_collect_kernel / cbh_walk2_interp_kernel): per evaluation-site slot a list of (request | program << 32)
-  CBH_G u32* site_cnt; CBH_G u64* site_list; u32 site_cap; u32 pad_sites;   // [slots], [slots][site_cap]; null = the fused pre-pass
+  CBH_G u32* site_cnt; CBH_G u64* site_list; u32 site_cap;   // [slots], [slots][site_cap]; null = the fused pre-pass
+  // The compact form of a resident batch (below, CBH_FI_COMPACT): narrow_cols bit k = cached column k has a 32-bit plane in `cval`,
+  // bit CBH_CI_ACT4 = every request has ACT_OFF = 4 * request and ACT_CNT = 4.  creq = the request records, or null.
+  u32 compact_info;
+  const CBH_G u32* creq; const CBH_G u32* cval;   // [n_requests][4]; [narrow columns, in column order][n_requests]
 };
+// The compact form of a resident batch's inputs, derived on the device from the wide arrays when the batch is uploaded
+// (cbh_compact_scan_kernel / cbh_compact_pack_kernel, cbh_check_flat.h) and read by the flat kernels' compact instantiations.
+// A request record is four words, record-major - everything flat_body takes from req_u32, roles and tuple_action:
+//   word 0  principal id
+//   word 1  kind (16) | resource version << 16                      (string ids; a batch with an id of 2^16 or more keeps the wide form)
+//   word 2  resource scope index (16) | role count << 16 (3) | action count << 19 (3) | role class 2 << 22 (5) | role class 3 << 27 (5)
+//   word 3  action classes 0..3 (5 each) | role class 0 << 20 | role class 1 << 25 | bit 30 spare | CBH_SCOPE_EXACT (bit 31)
+// The classes are what the wide prologue computes from the ids and the table's two class tables, clamps included (31 = a string no
+// rule names, or an action / role the request does not have): a resident batch is bound to one immutable table image.
+// A cached column whose values' high words are zero in every request of the batch has a plane of its low words in `cval`; the
+// others are read from col_val.  Tags stay as bytes in col_tag.
+#define CBH_CI_NARROW_MASK 0xFFFFu
+#define CBH_CI_ACT4 0x10000u
+#define CBH_CI_MISFIT 0x20000u   /* (the scan's verdict only, never in BatchDev: a field does not fit the record) */
+__host__ __device__ __forceinline__ u32 cbh_creq_w1(u32 kind, u32 ver) { return kind | (ver << 16); }
+__host__ __device__ __forceinline__ u32 cbh_creq_w2(u32 r_scope, u32 role_cnt, u32 act_cnt, u32 rc2, u32 rc3) {
+  return (r_scope & 0xFFFFu) | (role_cnt << 16) | (act_cnt << 19) | (rc2 << 22) | (rc3 << 27);
+}
+__host__ __device__ __forceinline__ u32 cbh_creq_w3(u32 r_scope, u32 ac0, u32 ac1, u32 ac2, u32 ac3, u32 rc0, u32 rc1) {
+  return ac0 | (ac1 << 5) | (ac2 << 10) | (ac3 << 15) | (rc0 << 20) | (rc1 << 25) | (r_scope & 0x80000000u);
+}
 
 struct OutDev {
   CBH_G u8* effect; CBH_G u32* policy; CBH_G u32* scope; CBH_G u8* status; CBH_G u64* edr;
@@ -144,7 +169,8 @@ struct __attribute__((aligned(16))) KernelArgs { TableDev t; BatchDev b; OutDev 
 #define CBH_FI_ONLY_WIDER 0x40000u  /* cbh_check_kernel*: only the requests no shape of the walk holds are this launch's */
 #define CBH_FI_PACKED_TAGS 0x80000u /* the column cache keeps a tag as a byte (CBH_CC_DWORDS): chosen per launch, where the smaller cache lets a CU hold more workgroups */
 #define CBH_FI_PACKED_RES 0x100000u /* the flat kernels write a packed word per tuple (cbh_pk_word) into OutDev.policy, and leave effect / status / scope alone */
-#define CBH_FI_MASK 0x1F0000u
+#define CBH_FI_COMPACT 0x200000u    /* the flat kernels' compact instantiations: the request records and 32-bit value planes (BatchDev.creq / cval); 0 = the wide arrays */
+#define CBH_FI_MASK 0x3F0000u
 #define CBH_W2_NA 8u
 #define CBH_W2_NR 4u
 #define CBH_W2_WIDE_NR 8u           /* the wider shapes: 8 actions x 8 roles (cbh_walk2_wide_kernel) ... */
