@@ -111,7 +111,7 @@ struct BatchDev {
 // rule names, or an action / role the request does not have): a resident batch is bound to one immutable table image.
 // A cached column whose values' high words are zero in every request of the batch has a plane of its low words in `cval`; the
 // others are read from col_val.  Tags stay as bytes in col_tag.
-#define CBH_CI_NARROW_MASK 0xFFFFu
+#define CBH_CI_NARROW_MASK 0xFFFFu   /* (one bit per cached column: a static_assert next to CBH_CACHE_COLS ties the two) */
 #define CBH_CI_ACT4 0x10000u
 #define CBH_CI_MISFIT 0x20000u   /* (the scan's verdict only, never in BatchDev: a field does not fit the record) */
 __host__ __device__ __forceinline__ u32 cbh_creq_w1(u32 kind, u32 ver) { return kind | (ver << 16); }
@@ -226,6 +226,9 @@ __device__ __forceinline__ Ctx ctx_from_memory(const KernelArgs* ka, const VmLds
              m.it_state, m.cc, m.n_cached & 0x7FFFFFFFu, ka};
 }
 #define CBH_CACHE_COLS 16
+// one bit of CBH_CI_NARROW_MASK per cached column: the scan kernel's `1u << k` must stay below CBH_CI_ACT4 / CBH_CI_MISFIT
+static_assert(CBH_CACHE_COLS <= 16 && (CBH_CI_NARROW_MASK >> (CBH_CACHE_COLS - 1)) != 0 && (CBH_CI_NARROW_MASK & (CBH_CI_ACT4 | CBH_CI_MISFIT)) == 0,
+              "the compact form's narrow-column mask has sixteen bits, right below its two flag bits");
 // dwords of one wave's column cache (cbh_check_wave.h fill_column_cache): [value low word][value high word], each [column][lane],
 // then the tags.  Two forms of those, chosen per launch (CBH_FI_PACKED_TAGS):
 //   wide    [column][lane] the aligned dword of the batch's tag bytes that holds the lane's - every load of the fill goes straight
