@@ -37,6 +37,7 @@ EXPORTED_SYMBOLS = [
     "cbh_wire_flatten", "cbh_wire_spans_download", "cbh_wire_outputs", "cbh_wire_check_pb", "cbh_wire_check_pb_submit", "cbh_wire_check_pb_collect",
     "cbh_wire_flatten_requests", "cbh_wire_check_requests_pb", "cbh_wire_check_requests_trail_pb", "cbh_batch_set_trail", "cbh_trail_download",
     "cbh_table_num_policies", "cbh_table_policy_key", "cbh_check_batch_trail",
+    "cbh_batch_upload_cross", "cbh_result_download_allow_bits",
 ]
 
 
@@ -75,6 +76,11 @@ class CTrace(C.Structure):
 
 class CWireInfo(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("n_requests", "n_tuples", "n_host", "first_bad", "dict_slots", "heap_len", "fill_runs", "n_routes")]
+
+
+class CCross(C.Structure):
+    _fields_ = [("n_principals", C.c_uint32), ("n_resources", C.c_uint32), ("n_actions", C.c_uint32),
+                ("action_ids", C.c_void_p), ("p_order", C.c_void_p), ("r_order", C.c_void_p)]
 
 
 class HostFlattenerNeeded(RuntimeError):
@@ -190,6 +196,10 @@ def load():
     lib.cbh_trail_download.restype = i32
     lib.cbh_check_batch_trail.argtypes = [vp, C.POINTER(CBatch), C.POINTER(CParams), C.POINTER(CResult), vp, u32, vp]
     lib.cbh_check_batch_trail.restype = i32
+    lib.cbh_batch_upload_cross.argtypes = [vp, u32, C.POINTER(CBatch), C.POINTER(CCross), C.POINTER(vp)]
+    lib.cbh_batch_upload_cross.restype = i32
+    lib.cbh_result_download_allow_bits.argtypes = [vp, vp, vp, C.c_size_t]
+    lib.cbh_result_download_allow_bits.restype = i32
     _lib = lib
     return lib
 
@@ -403,6 +413,31 @@ class Table:
         h = C.c_void_p()
         _check(load().cbh_batch_upload_on(self.h, device_index, C.byref(cb), C.byref(h)))
         return DeviceBatch(self, h, batch.n_tuples, batch.n_requests, batch)
+
+    def upload_cross(self, halves_batch, n_principals, n_resources, action_ids, p_order=None, r_order=None, device_index=0):
+        """``cbh_batch_upload_cross``: ``halves_batch`` holds ``n_principals`` + ``n_resources`` flattened requests (principals
+        first); the device builds the resident batch of their product - request ``j' * n_principals + i'`` pairs resource
+        ``r_order[j']`` with principal ``p_order[i']`` (None = identity), every request asking for ``action_ids`` (string ids)."""
+        cb = make_cbatch(halves_batch, self.num_columns)
+        act = np.ascontiguousarray(action_ids, dtype=np.uint32)
+        po = None if p_order is None else np.ascontiguousarray(p_order, dtype=np.uint32)
+        ro = None if r_order is None else np.ascontiguousarray(r_order, dtype=np.uint32)
+        if (po is not None and po.size != n_principals) or (ro is not None and ro.size != n_resources):
+            raise ValueError("p_order / r_order must have one entry per principal / resource")
+        x = CCross(n_principals, n_resources, act.size, act.ctypes.data if act.size else None,
+                   po.ctypes.data if po is not None and po.size else None, ro.ctypes.data if ro is not None and ro.size else None)
+        h = C.c_void_p()
+        _check(load().cbh_batch_upload_cross(self.h, device_index, C.byref(cb), C.byref(x), C.byref(h)))
+        nm = int(n_principals) * int(n_resources)
+        return DeviceBatch(self, h, nm * int(act.size), nm)
+
+    def download_allow_bits(self, dbatch, into=None):
+        """``cbh_result_download_allow_bits`` -> uint64[(n_tuples + 63) // 64]: bit k = tuple k (device order) of the last
+        ``launch`` is EFFECT_ALLOW.  ``into``: a uint64 array to reuse (page-locked: ``pinned_empty``)."""
+        words = (dbatch.n_tuples + 63) // 64
+        bits = into if into is not None else np.zeros(words, dtype=np.uint64)
+        _check(load().cbh_result_download_allow_bits(self.h, dbatch.h, bits.ctypes.data if bits.size else None, bits.size))
+        return bits[:words]
 
     def wire_flatten(self, data, offsets, default_policy_version="default", default_scope="", device_index=0, globals_pb=b""):
         """``cbh_wire_flatten``: serialized CheckInputs (uint8 array + uint64[n + 1] offsets) -> a resident batch the GPU

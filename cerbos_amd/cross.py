@@ -26,10 +26,9 @@ P_FIELDS = (RQ_PRINCIPAL_ID, RQ_P_SCOPE, RQ_P_VERSION, RQ_ROLE_OFF, RQ_ROLE_CNT,
 R_FIELDS = (RQ_KIND, RQ_R_SCOPE, RQ_R_VERSION, RQ_S_RESOURCE_ID, RQ_S_KIND, RQ_S_R_SCOPE, RQ_S_R_VERSION)
 
 
-def cross_product_batch(flattener, columns, principals, resources, actions, aux_data=None,
-                        default_policy_version="default", default_scope="", sort=True) -> Batch:
-    """``flattener``: ``flatten.Flattener`` or ``ingest.WireFlattener``; ``columns``: ``LoweredTable.columns``.
-    ``aux_data`` (one dict, or one per principal) is visible to every request of that principal."""
+def cross_halves(flattener, principals, resources, actions, aux_data, default_policy_version, default_scope, sort):
+    """The N + M halves flattened in one call (principals first; input 0 carries the actions) and the orders of the product:
+    -> (halves batch, p_order, r_order, action ids)."""
     n, m, a = len(principals), len(resources), len(actions)
     if a > 64:
         raise ValueError("at most 64 actions per cross-product batch")
@@ -40,9 +39,8 @@ def cross_product_batch(flattener, columns, principals, resources, actions, aux_
     halves += [{"principal": blank_p, "resource": r, "actions": []} for r in resources]
     h = flattener.flatten(halves, default_policy_version, default_scope, sort=False)
     assert h.n_requests == n + m
-    nm = n * m
     hp, hr = h.req_u32[:, :n], h.req_u32[:, n:]
-    if sort and nm > 1:
+    if sort and n * m > 1:
         # principals by (role count, order-sensitive role-list signature), resources by (kind, version, scope):
         # the keys of flatten.sort_batch_by_route, applied to the halves
         cnt = hp[RQ_ROLE_CNT].astype(np.int64)
@@ -56,6 +54,18 @@ def cross_product_batch(flattener, columns, principals, resources, actions, aux_
         r_order = np.lexsort((hr[RQ_R_SCOPE], hr[RQ_R_VERSION], hr[RQ_KIND]))
     else:
         p_order, r_order = np.arange(n), np.arange(m)
+    act_ids = h.tuple_action[:a] if a else np.zeros(0, dtype=np.uint32)     # input 0 carried the actions
+    return h, p_order, r_order, act_ids
+
+
+def cross_product_batch(flattener, columns, principals, resources, actions, aux_data=None,
+                        default_policy_version="default", default_scope="", sort=True) -> Batch:
+    """``flattener``: ``flatten.Flattener`` or ``ingest.WireFlattener``; ``columns``: ``LoweredTable.columns``.
+    ``aux_data`` (one dict, or one per principal) is visible to every request of that principal."""
+    n, m, a = len(principals), len(resources), len(actions)
+    h, p_order, r_order, act_ids = cross_halves(flattener, principals, resources, actions, aux_data, default_policy_version, default_scope, sort)
+    nm = n * m
+    hp, hr = h.req_u32[:, :n], h.req_u32[:, n:]
     b = Batch()
     b.n_requests, b.n_tuples, b.n_strings = nm, nm * a, h.n_strings
     req = np.zeros((RQ_NFIELDS, nm), dtype=np.uint32)
@@ -74,7 +84,6 @@ def cross_product_batch(flattener, columns, principals, resources, actions, aux_
             b.col_tag[c], b.col_val[c] = np.repeat(h.col_tag[c, n:][r_order], n), np.repeat(h.col_val[c, n:][r_order], n)
         else:       # principal attributes and auxiliary data travel with the principal
             b.col_tag[c], b.col_val[c] = np.tile(h.col_tag[c, :n][p_order], m), np.tile(h.col_val[c, :n][p_order], m)
-    act_ids = h.tuple_action[:a] if a else np.zeros(0, dtype=np.uint32)     # input 0 carried the actions
     b.tuple_action = np.tile(act_ids, nm).astype(np.uint32)
     b.tuple_req = np.repeat(np.arange(nm, dtype=np.uint32), a)
     b.roles, b.heap_tag, b.heap_val = h.roles, h.heap_tag, h.heap_val
@@ -84,6 +93,33 @@ def cross_product_batch(flattener, columns, principals, resources, actions, aux_
     b.shape = (n, m, a)
     b.p_order, b.r_order = p_order, r_order
     return b
+
+
+def cross_product_upload(table, flattener, columns, principals, resources, actions, aux_data=None,
+                         default_policy_version="default", default_scope="", sort=True, device_index=0):
+    """The same product built ON THE DEVICE (``capi.Table.upload_cross``): only the N + M halves cross the host link.  Returns the
+    resident batch (``capi.DeviceBatch``) with ``shape``, ``p_order``, ``r_order``, so ``effect_cube`` / ``result_cubes`` /
+    ``allow_cube`` accept it.  ``columns`` is accepted for symmetry with ``cross_product_batch``: which half a column comes from
+    is read off the table image."""
+    h, p_order, r_order, act_ids = cross_halves(flattener, principals, resources, actions, aux_data, default_policy_version, default_scope, sort)
+    return upload_halves(table, h, len(principals), len(resources), act_ids, p_order, r_order, device_index)
+
+
+def upload_halves(table, halves, n, m, act_ids, p_order, r_order, device_index=0):
+    """``cross_product_upload`` for halves that are flattened already (a caller who keeps them across policy changes);
+    an order of None is the identity."""
+    db = table.upload_cross(halves, n, m, act_ids, p_order, r_order, device_index=device_index)
+    db.shape = (n, m, len(act_ids))
+    db.p_order = np.arange(n) if p_order is None else np.asarray(p_order)
+    db.r_order = np.arange(m) if r_order is None else np.asarray(r_order)
+    return db
+
+
+def allow_cube(batch, bits):
+    """``capi.Table.download_allow_bits`` of the batch -> bool[n][m][a]: [i][j][k] = principals[i] may actions[k] on resources[j]."""
+    n, m, a = batch.shape
+    allowed = np.unpackbits(np.ascontiguousarray(bits, dtype="<u8").view(np.uint8), count=n * m * a, bitorder="little").astype(bool)
+    return _cube(batch, allowed)
 
 
 def _cube(batch, per_tuple):

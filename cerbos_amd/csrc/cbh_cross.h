@@ -1,0 +1,81 @@
+// Cross-product batches built on the device (cerbos_hip.h cbh_batch_upload_cross) and the allow bitmap of a resident batch
+// (cbh_result_download_allow_bits).  Three small kernels, none of them on the decision path: the product they build is an ordinary
+// resident batch the decision kernels read unchanged.
+//
+// The product's layout: N principals x M resources, resource-major.  Device request q = j' * N + i' pairs the
+// j'-th resource with the i'-th principal of the caller's orders; the halves batch holds the N principals in its first N
+// requests and the M resources in its last M.  Roles, heap and strings are the halves' own arrays, shared by every request.
+#pragma once
+#include "cbh_interp.h"
+
+struct CrossArgs {
+  // the halves as uploaded: [CBH_RQ_NFIELDS][nh], [n_columns][nh], [n_columns][nh], nh = n + m
+  const CBH_G u32* h_req; const CBH_G u8* h_tag; const CBH_G u64* h_val;
+  const CBH_G u32* p_order; const CBH_G u32* r_order;   // [n], [m], or null = identity
+  const CBH_G u8* col_side;                             // [n_columns] 1 = the column travels with the resource (root R.attr), 0 = with the principal
+  const CBH_G u32* action_ids;                          // [a]
+  CBH_G u32* req; CBH_G u8* tag; CBH_G u64* val;        // the product: [CBH_RQ_NFIELDS][nm], [n_columns][nm], [n_columns][nm]
+  CBH_G u32* tuple_action;                              // [nm * a]
+  u32 n, m, a, n_columns;
+};
+
+// which half a request field comes from: bit f set = the resource's (cerbos_amd/cross.py R_FIELDS); ACT_OFF / ACT_CNT are computed
+#define CBH_CROSS_R_FIELDS ((1u << CBH_RQ_KIND) | (1u << CBH_RQ_R_SCOPE) | (1u << CBH_RQ_R_VERSION) | (1u << CBH_RQ_S_RESOURCE_ID) | \
+                            (1u << CBH_RQ_S_KIND) | (1u << CBH_RQ_S_R_SCOPE) | (1u << CBH_RQ_S_R_VERSION))
+
+// One lane per device request.  Consecutive lanes are consecutive principals of one resource: principal-side loads are coalesced
+// (or a gather through p_order out of N rows that stay in cache), resource-side loads hit one or two rows per wave, and every
+// store goes to [field or column][q] - 64 consecutive elements per wave instruction.  A pure stream: nm * (64 + 9 * n_columns) bytes out.
+__global__ __launch_bounds__(256) void cbh_cross_expand_kernel(CrossArgs x) {
+  const u64 q64 = (u64)blockIdx.x * 256u + threadIdx.x;   // (n * m may lie within a workgroup of 2^32)
+  const u32 nm = x.n * x.m;
+  if (q64 >= nm) return;
+  const u32 q = (u32)q64;
+  const u32 jp = q / x.n, ip = q - jp * x.n;
+  const size_t NH = (size_t)x.n + x.m, NM = nm;
+  const size_t pi = x.p_order ? x.p_order[ip] : ip;                    // the principal's row of the halves
+  const size_t ri = (size_t)x.n + (x.r_order ? x.r_order[jp] : jp);    // the resource's
+#pragma unroll
+  for (u32 f = 0; f < CBH_RQ_NFIELDS; ++f) {
+    u32 v;
+    if (f == CBH_RQ_ACT_OFF) v = q * x.a;
+    else if (f == CBH_RQ_ACT_CNT) v = x.a;
+    else v = x.h_req[f * NH + (((CBH_CROSS_R_FIELDS >> f) & 1u) ? ri : pi)];
+    x.req[f * NM + q] = v;
+  }
+  for (u32 c = 0; c < x.n_columns; ++c) {
+    const size_t src = c * NH + (x.col_side[c] ? ri : pi);
+    x.tag[c * NM + q] = x.h_tag[src];
+    x.val[c * NM + q] = x.h_val[src];
+  }
+}
+
+// tuple_action = the A ids repeated nm times: one lane per four words, a 16-byte store each (the array starts a device allocation,
+// so word 4 t is 16-byte aligned); the last lane writes what is left word by word.
+__global__ __launch_bounds__(256) void cbh_cross_actions_kernel(CrossArgs x) {
+  const u64 total = (u64)x.n * x.m * x.a;
+  const u64 w = ((u64)blockIdx.x * 256u + threadIdx.x) * 4u;
+  if (w >= total) return;
+  u32 k = (u32)(w % x.a);
+  u32 v[4];
+  for (u32 e = 0; e < 4; ++e) { v[e] = x.action_ids[k]; k = k + 1u == x.a ? 0u : k + 1u; }
+  if (w + 4u <= total) {
+    uint4 o; o.x = v[0]; o.y = v[1]; o.z = v[2]; o.w = v[3];
+    *reinterpret_cast<CBH_G uint4*>(x.tuple_action + w) = o;
+  } else {
+    for (u32 e = 0; w + e < total; ++e) x.tuple_action[w + e] = v[e];
+  }
+}
+
+// The allow bitmap: bit k of bits[k >> 6] = tuple k's effect is CBH_EFFECT_ALLOW.  One lane per tuple; the effect comes from the
+// packed result word where the last launch wrote that form (`packed`, cbh_pk_effect), else from the effect bytes; the wave ballots
+// and its first lane stores the word.  Lanes behind the last tuple vote no, so the last word's unused bits are 0.  Every lane
+// reaches the ballot (cbh_interp.h's discipline).
+struct AllowBitsArgs { const CBH_G u32* packed; const CBH_G u8* effect; CBH_G u64* bits; u32 n_tuples; u32 pad; };
+__global__ __launch_bounds__(256) void cbh_allow_bits_kernel(AllowBitsArgs a) {
+  const u64 k = (u64)blockIdx.x * 256u + threadIdx.x;
+  u32 eff = 0;
+  if (k < a.n_tuples) eff = a.packed ? cbh_pk_effect(a.packed[k]) : (u32)a.effect[k];
+  const u64 mask = wave_ballot(eff == CBH_EFFECT_ALLOW);
+  if ((threadIdx.x & 63u) == 0u && k < a.n_tuples) a.bits[k >> 6] = mask;
+}

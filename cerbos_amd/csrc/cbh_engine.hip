@@ -231,6 +231,7 @@ struct cbh_device_batch {
   bool res_packed = false; bool edr_zero = false;
   // The batch has its compact form (cbh_vm.h BatchDev.creq / cval; batch_compact below): the flat kernels' compact instantiations read it.
   bool compact = false;
+  u64* allow_bits = nullptr;   // cbh_result_download_allow_bits: the bitmap's device words, allocated at the first call
   const u64* w_moff = nullptr; u32 w_dver_off = 0, w_dver_len = 0;   // (the device assembler reads the messages again)
   bool w_total_known = false; uint64_t w_total = 0; uint32_t w_out_errors = 0;   // cbh_wire_outputs ran its size / scan launches for this batch's current results
   u32* w_sizes = nullptr; u64* w_wavesum = nullptr; u64* w_waveoff = nullptr; WireOutStats* w_ostats = nullptr; u64* w_out_off = nullptr; u8* w_out_flags = nullptr;
@@ -579,6 +580,23 @@ static int batch_compact(cbh_device_batch* b, hipStream_t s) {
   return 0;
 }
 
+// what a resident batch owns beside its inputs: glob bits, evaluation-site results, the result arrays, the launch arguments
+// (b->dev's counts and b->plain_tags are set)
+static int batch_device_buffers(cbh_device_batch* b) {
+  BatchDev& d = b->dev; const Replica* rep = b->rep;
+  int rc = dalloc(b, d.gbits, (size_t)3 * d.n_strings);
+  d.n_gwords = (rep->dev.flags & CBH_MF_WALK2) ? w2_gwords(rep->dev.gslots_generic, rep->dev.gslots_all, b->plain_tags) : 0;
+  d.n_gslots = 0;   // per launch (launch_plan)
+  if (d.n_gwords) rc |= dalloc(b, d.gres, (size_t)d.n_gwords * d.n_requests); else d.gres = nullptr;
+  rc |= dalloc(b, b->out.effect, d.n_tuples);
+  rc |= dalloc(b, b->out.policy, d.n_tuples);
+  rc |= dalloc(b, b->out.scope, d.n_tuples);
+  rc |= dalloc(b, b->out.status, d.n_tuples);
+  rc |= dalloc(b, b->out.edr, d.n_requests);
+  rc |= dalloc(b, b->d_args, 1);
+  return rc;
+}
+
 static int batch_upload(cbh_table* t, uint32_t device_index, const cbh_batch* in, cbh_device_batch** out, bool compact) {
   if (!t || !in || !out) return fail("null argument");
   if (device_index >= t->reps.size()) return fail("device index out of range");
@@ -610,16 +628,7 @@ static int batch_upload(cbh_table* t, uint32_t device_index, const cbh_batch* in
   rc |= up(b, d.str_off, in->str_off, in->n_strings ? (size_t)in->n_strings + 1 : 0, s);
   rc |= up(b, d.str_bytes, in->str_bytes, in->str_bytes_len, s);
   rc |= up(b, d.str_flags, in->str_flags, in->n_strings, s);
-  rc |= dalloc(b, d.gbits, (size_t)3 * in->n_strings);
-  d.n_gwords = (rep->dev.flags & CBH_MF_WALK2) ? w2_gwords(rep->dev.gslots_generic, rep->dev.gslots_all, b->plain_tags) : 0;
-  d.n_gslots = 0;   // per launch (launch_plan)
-  if (d.n_gwords) rc |= dalloc(b, d.gres, (size_t)d.n_gwords * NR); else d.gres = nullptr;
-  rc |= dalloc(b, b->out.effect, in->n_tuples);
-  rc |= dalloc(b, b->out.policy, in->n_tuples);
-  rc |= dalloc(b, b->out.scope, in->n_tuples);
-  rc |= dalloc(b, b->out.status, in->n_tuples);
-  rc |= dalloc(b, b->out.edr, NR);
-  rc |= dalloc(b, b->d_args, 1);
+  rc |= batch_device_buffers(b);
   if (rc != 0) { cbh_batch_release(b); return -1; }
   // glob bits of the batch-local strings: all zero unless the table has automata to run (then
   // cbh_check_resident overwrites every word on each launch)
@@ -633,6 +642,116 @@ static int batch_upload(cbh_table* t, uint32_t device_index, const cbh_batch* in
 }
 extern "C" int cbh_batch_upload_on(cbh_table* t, uint32_t device_index, const cbh_batch* in, cbh_device_batch** out) { return batch_upload(t, device_index, in, out, true); }
 extern "C" int cbh_batch_upload(cbh_table* t, const cbh_batch* in, cbh_device_batch** out) { return cbh_batch_upload_on(t, 0, in, out); }
+
+// ---- cross-product batches: N + M halves up, the N x M product built in device memory (cbh_cross.h) ------------------------
+// The batch's shape comes from the halves, looking only at the rows the product uses, so that the product gets the plan a
+// host-built batch of the same requests gets (validate_batch's answers for that batch, without the batch).
+static int cross_upload(cbh_table* t, uint32_t device_index, const cbh_batch* h, const cbh_cross* x, cbh_device_batch** out) {
+  if (!t || !h || !x || !out) return fail("null argument");
+  *out = nullptr;
+  if (device_index >= t->reps.size()) return fail("device index out of range");
+  const u64 N = x->n_principals, M = x->n_resources, A = x->n_actions;
+  if (!N || !M || !A) return fail("cbh_cross: n_principals, n_resources and n_actions must be at least 1");
+  if (A > CBH_MAX_ACTIONS_PER_REQUEST) return fail("cbh_cross: more than CBH_MAX_ACTIONS_PER_REQUEST actions");
+  if (!x->action_ids) return fail("null argument");
+  if ((u64)h->n_requests != N + M) return fail("cbh_cross: the halves batch must hold n_principals + n_resources requests");
+  if (N * M >= (1ull << 32) || N * M * A >= (1ull << 32)) return fail("cbh_cross: the product has 2^32 requests or tuples, or more: split the resources");
+  const u32 ncol = h->n_columns;
+  if (ncol != t->meta[CBH_M_NCOLUMNS]) return fail("cbh_batch.n_columns does not match the table's column schema");
+  if (t->wire.cols.size() < ncol) return fail("the image names no column paths (CBH_SEC_COLUMN_PATHS): which half a column comes from is unknown");
+  if (!h->req_u32 || (h->n_roles && !h->roles) || (ncol && (!h->col_tag || !h->col_val)) || (h->heap_len && (!h->heap_tag || !h->heap_val)) ||
+      (h->n_strings && (!h->str_off || !h->str_flags)) || (h->str_bytes_len && !h->str_bytes)) return fail("cbh_batch: a required array is NULL");
+  if (h->n_strings && h->str_off[h->n_strings] > h->str_bytes_len) return fail("cbh_batch: string offsets exceed str_bytes_len");
+  const size_t NH = (size_t)(N + M), NM = (size_t)(N * M), NT = (size_t)(N * M * A);
+  std::vector<u8> side, seen;
+  try { side.assign(ncol ? ncol : 1, 0); seen.assign(std::max(N, M), 0); } catch (...) { return fail("out of memory"); }
+  for (u32 c = 0; c < ncol; ++c) side[c] = t->wire.cols[c].root == 1 ? 1 : 0;
+  for (int which = 0; which < 2; ++which) {   // the orders are permutations
+    const uint32_t* ord = which ? x->r_order : x->p_order; const u64 cnt = which ? M : N;
+    if (!ord) continue;
+    std::fill(seen.begin(), seen.begin() + cnt, (u8)0);
+    for (u64 i = 0; i < cnt; ++i) {
+      if (ord[i] >= cnt || seen[ord[i]]) return fail(which ? "cbh_cross: r_order is not a permutation of 0 .. n_resources - 1" : "cbh_cross: p_order is not a permutation of 0 .. n_principals - 1");
+      seen[ord[i]] = 1;
+    }
+  }
+  // roles of the principals; where the requests wider than the walk's base shape lie in the product (validate_batch's wide_lo / wide_hi)
+  const u32* role_off = h->req_u32 + (size_t)CBH_RQ_ROLE_OFF * NH; const u32* role_cnt = h->req_u32 + (size_t)CBH_RQ_ROLE_CNT * NH;
+  u32 maxr = 0, bad = 0; u64 ilo = N, ihi = 0;   // device positions i' of the principals with more than CBH_W2_NR roles
+  for (u64 ip = 0; ip < N; ++ip) {
+    const size_t i = x->p_order ? x->p_order[ip] : ip;
+    maxr = role_cnt[i] > maxr ? role_cnt[i] : maxr;
+    bad |= (u32)((u64)role_off[i] + role_cnt[i] > (u64)h->n_roles);
+    if (role_cnt[i] > CBH_W2_NR) { if (ilo == N) ilo = ip; ihi = ip + 1; }
+  }
+  if (bad) return fail("cbh_batch: a request's role or action slice lies outside the batch");
+  u32 wide_lo = 0, wide_hi = 0;
+  if (A > CBH_W2_NA) wide_hi = (u32)NM;
+  else if (ihi) { wide_lo = (u32)ilo; wide_hi = (u32)((M - 1) * N + ihi); }
+  // plain tags: BatchShape::plain_tags over the rows the product uses
+  bool plain = true;
+  {
+    const u32 mf = t->meta[CBH_M_FLAGS];
+    const bool matters = ((mf & CBH_MF_FLAT) && A <= 4 && maxr <= 4) || ((mf & CBH_MF_WALK2) && t->meta[CBH_M_GSLOTS_ALL] > t->meta[CBH_M_GSLOTS_GENERIC]);
+    u32 sens = t->meta[CBH_M_SENS_COLS];
+    if (ncol < 32) sens &= (1u << ncol) - 1u;
+    static const bool force_any = getenv("CBH_FLAT_ANY") != nullptr;
+    bool hit = false;
+    if (matters) for (u32 c = 0; c < 32 && c < ncol && !hit; ++c) if ((sens >> c) & 1u)
+      hit = side[c] ? BatchShape::has_int_or_container_tag(h->col_tag + (size_t)c * NH + N, M) : BatchShape::has_int_or_container_tag(h->col_tag + (size_t)c * NH, N);
+    plain = !force_any && !hit;
+  }
+  Replica* rep = t->reps[device_index];
+  HIPCHK(hipSetDevice(rep->device));
+  cbh_device_batch* b = new (std::nothrow) cbh_device_batch();
+  if (!b) return fail("out of memory");
+  cbh_table_retain(t);
+  b->table = t; b->rep = rep; b->max_actions = (u32)A; b->max_roles = maxr; b->plain_tags = plain; b->wide_lo = wide_lo; b->wide_hi = wide_hi;
+  BatchDev& d = b->dev;
+  d.n_requests = (u32)NM; d.n_tuples = (u32)NT; d.n_roles = h->n_roles; d.n_columns = ncol; d.n_strings = h->n_strings; d.heap_len = h->heap_len;
+  d.req_lo = 0; d.req_hi = (u32)NM;
+  b->stream = rep->rstreams[rep->next_rstream.fetch_add(1, std::memory_order_relaxed) % (uint32_t)rep->n_rstreams.load(std::memory_order_relaxed)];
+  hipStream_t s = b->stream;
+  CrossArgs ca{};
+  ca.n = (u32)N; ca.m = (u32)M; ca.a = (u32)A; ca.n_columns = ncol;
+  int rc = 0;
+  // the halves, the orders, the sides and the action ids (they stay with the batch until it is released: N + M rows)
+  rc |= up(b, ca.h_req, h->req_u32, (size_t)CBH_RQ_NFIELDS * NH, s);
+  rc |= up(b, ca.h_tag, h->col_tag, (size_t)ncol * NH, s);
+  rc |= up(b, ca.h_val, h->col_val, (size_t)ncol * NH, s);
+  if (x->p_order) rc |= up(b, ca.p_order, x->p_order, (size_t)N, s);
+  if (x->r_order) rc |= up(b, ca.r_order, x->r_order, (size_t)M, s);
+  rc |= up(b, ca.col_side, (const u8*)side.data(), (size_t)ncol, s);
+  rc |= up(b, ca.action_ids, x->action_ids, (size_t)A, s);
+  // shared as they are
+  rc |= up(b, d.roles, h->roles, h->n_roles, s);
+  rc |= up(b, d.heap_tag, h->heap_tag, h->heap_len, s);
+  rc |= up(b, d.heap_val, h->heap_val, h->heap_len, s);
+  rc |= up(b, d.str_off, h->str_off, h->n_strings ? (size_t)h->n_strings + 1 : 0, s);
+  rc |= up(b, d.str_bytes, h->str_bytes, h->str_bytes_len, s);
+  rc |= up(b, d.str_flags, h->str_flags, h->n_strings, s);
+  // the product
+  d.tuple_req = nullptr;
+  rc |= dalloc(b, ca.req, (size_t)CBH_RQ_NFIELDS * NM);
+  rc |= dalloc(b, ca.tag, (size_t)ncol * NM);
+  rc |= dalloc(b, ca.val, (size_t)ncol * NM);
+  rc |= dalloc(b, ca.tuple_action, NT);
+  rc |= batch_device_buffers(b);
+  if (rc != 0) { cbh_batch_release(b); return -1; }
+  d.req_u32 = ca.req; d.col_tag = ca.tag; d.col_val = ca.val; d.tuple_action = ca.tuple_action;
+  if (h->n_strings && hipMemsetAsync(d.gbits, 0, (size_t)3 * h->n_strings * sizeof(u64), s) != hipSuccess) { cbh_batch_release(b); return fail("upload failed"); }
+  hipLaunchKernelGGL(cbh_cross_expand_kernel, dim3((u32)((NM + 255u) / 256u)), dim3(256), 0, s, ca);
+  hipLaunchKernelGGL(cbh_cross_actions_kernel, dim3((u32)(((NT + 3u) / 4u + 255u) / 256u)), dim3(256), 0, s, ca);
+  if (hipGetLastError() != hipSuccess) { cbh_batch_release(b); return fail("cross-product expansion failed to launch"); }
+  // (`side` is pageable memory of this frame: its copy must have left before the frame goes - batch_compact synchronises, or the wait below)
+  if (batch_compact(b, s) != 0) { cbh_batch_release(b); return -1; }
+  if (hipStreamSynchronize(s) != hipSuccess) { cbh_batch_release(b); return fail("upload failed"); }
+  *out = b;
+  return 0;
+}
+extern "C" int cbh_batch_upload_cross(cbh_table* t, uint32_t device_index, const cbh_batch* halves, const cbh_cross* x, cbh_device_batch** out) {
+  try { return cross_upload(t, device_index, halves, x, out); } catch (...) { return fail("out of memory"); }
+}
 
 static void collect_slot(Replica* r, Replica::Slot& sl) {   // the slot's last event has completed
   if (!sl.pending) return;
@@ -919,6 +1038,29 @@ extern "C" int cbh_result_download(cbh_table* t, cbh_device_batch* b, cbh_result
     }
     HIPCHK(hipMemcpyAsync(out->edr_mask, src, (size_t)d.n_requests * 8, hipMemcpyDeviceToHost, s));
   }
+  HIPCHK(hipStreamSynchronize(s));
+  collect_times(rep);
+  return 0;
+}
+
+// One bit per tuple instead of at least one byte: the bitmap is made on the device from whichever form the last launch wrote (the
+// packed words are NOT unpacked: the batch's results stay as they are for a later cbh_result_download) and crosses by itself.
+extern "C" int cbh_result_download_allow_bits(cbh_table* t, cbh_device_batch* b, uint64_t* bits, size_t n_words) {
+  if (!t || !b || !bits) return fail("null argument");
+  if (b->table != t) return fail("batch was uploaded for a different table");
+  const size_t need = ((size_t)b->dev.n_tuples + 63) / 64;
+  if (n_words < need) return fail("cbh_result_download_allow_bits: the buffer is shorter than (n_tuples + 63) / 64 words");
+  if (!need) return 0;
+  Replica* rep = b->rep;
+  std::lock_guard<std::mutex> lk(rep->mu);
+  HIPCHK(hipSetDevice(rep->device));
+  hipStream_t s = b->stream;
+  if (!b->allow_bits && dalloc(b, b->allow_bits, need) != 0) { b->allow_bits = nullptr; return -1; }
+  AllowBitsArgs a{};
+  a.packed = b->res_packed ? b->out.policy : nullptr; a.effect = b->out.effect; a.bits = b->allow_bits; a.n_tuples = b->dev.n_tuples;
+  hipLaunchKernelGGL(cbh_allow_bits_kernel, dim3((u32)(((size_t)b->dev.n_tuples + 255u) / 256u)), dim3(256), 0, s, a);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(bits, b->allow_bits, need * 8, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   collect_times(rep);
   return 0;

@@ -259,6 +259,44 @@ int cbh_result_download(cbh_table* t, cbh_device_batch* b, cbh_result* out);
  * launches, measured with HIP events on the library's own stream. */
 int cbh_kernel_time_ms(cbh_table* t, float* check_kernel_ms, float* resolve_kernel_ms);
 
+/* ---- Cross-product batches: N principals x M resources x A actions from N + M flattened requests ----------------
+ * The bulk question "which of these principals may do what to which of these resources" (access reviews, what-if runs after a
+ * policy change) has N + M messages of input and N * M * A decisions of work.  The halves cross the host link once, the device
+ * expands them into an ordinary resident batch (cerbos_amd/csrc/cbh_cross.h), the decision kernels decide it unchanged, and one
+ * bit per tuple comes back.
+ *
+ * `halves`: an ordinary flattened batch of N + M requests - the first N carry the principals (and whatever travels with a
+ * principal: auxData, per-call globals), the last M the resources; its own actions / tuples are not read.
+ * cbh_batch_upload_cross builds, in device memory, the resident batch of N * M requests and N * M * A tuples in which request
+ * q = j' * N + i' pairs resource j' with principal i' (resource-major; tuple q * A + k is action k), and returns it as any other
+ * resident batch: cbh_check_resident(_many), cbh_plan_describe, cbh_result_download, cbh_batch_release work on it unchanged.
+ *  - Which half a column comes from is read off the image: the columns of root R.attr from the resource, every other root
+ *    (P.attr, auxData.jwt / jwts, the call's globals) from the principal.
+ *  - roles, the heap and the strings are the halves' own arrays, uploaded once; ROLE_OFF / ROLE_CNT are the principal's,
+ *    ACT_OFF = q * A, ACT_CNT = A.
+ *  - The batch's shape (which kernels decide it) is derived from the rows the product uses, so the product gets the plan a
+ *    host-built batch of the same requests gets, the compact input form of flat tables included.
+ *  - p_order / r_order let the caller lay the product out in routing order (principals by role list, resources by kind,
+ *    version and scope) without sorting N * M requests; results come back in device order.
+ * Refused (< 0, cbh_last_error): a null argument, halves->n_requests != N + M, N, M or A of 0, A above
+ * CBH_MAX_ACTIONS_PER_REQUEST, N * M or N * M * A of 2^32 or more, an order that is not a permutation, a device index out of
+ * range, a device allocation that fails.
+ * Not here: one product sharded over several devices (split the resources and call once per device);
+ * cbh_check_batch_trail / cbh_trace_batch on a product (flatten the few inputs marked CBH_ST_CEL_ERROR / CBH_ST_WANTS_TRACE
+ * explicitly and trace those); deciding straight from the halves without materialising the product. */
+#define CBH_HAS_CROSS 1
+typedef struct cbh_cross {
+  uint32_t n_principals, n_resources, n_actions; /* N, M, A */
+  const uint32_t* action_ids; /* [A] string ids, as in cbh_batch.tuple_action: every request asks for these, in this order */
+  const uint32_t* p_order;    /* [N] or NULL (identity): device principal i' is halves request p_order[i']     */
+  const uint32_t* r_order;    /* [M] or NULL (identity): device resource  j' is halves request N + r_order[j'] */
+} cbh_cross;
+int cbh_batch_upload_cross(cbh_table* t, uint32_t device_index, const cbh_batch* halves, const cbh_cross* x, cbh_device_batch** out);
+/* Bit k of `bits` (bits[k >> 6] >> (k & 63) & 1) = tuple k of the last cbh_check_resident on `b` is CBH_EFFECT_ALLOW; tuples in
+ * the batch's device order, unused bits of the last word 0; n_words >= (n_tuples + 63) / 64 or the call fails and writes
+ * nothing.  Any resident batch; a later cbh_result_download still gives the full results. */
+int cbh_result_download_allow_bits(cbh_table* t, cbh_device_batch* b, uint64_t* bits, size_t n_words);
+
 /* ---- Device-side ingest: serialized CheckInputs in, a resident batch out (the GPU flattens) ----------------------
  * The reference decodes each CheckInput and builds its request view on the CPU (internal/ruletable/check.go:536-554); so did
  * libcerbos_ingest.so (cbi_flatten_pb).  cbh_wire_flatten uploads the raw messages - `bytes`, message i =

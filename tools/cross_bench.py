@@ -1,0 +1,158 @@
+#!/usr/bin/env python3
+"""End-to-end rate of a cross-product review (N principals x M resources x A actions), halves already flattened:
+
+  host leg    what a caller had before cbh_batch_upload_cross: cross_product_batch (numpy lays out N * M rows on the host) +
+              Table.upload (all N * M rows cross the link) + launch + download(want=()) (one byte per tuple back)
+  device leg  upload_cross (N + M rows up, the device expands them) + launch + download_allow_bits (one bit per tuple back)
+
+per configuration: 3 warm-ups, then at least 10 timed repetitions of each leg, wall clock from a synchronised device to the last
+byte on the host; min / median / max in decisions per second.  Plus the launch alone for both batches (the resident batch is the
+same, so it must not differ).
+
+  python tools/cross_bench.py                      both legs, C2 and T, 1024 x 1024 and 4096 x 1024, A = 4
+  python tools/cross_bench.py --host-only          the host leg alone: runs on a commit that has no device leg (the baseline; this
+                                                   file is the only one copied over)
+  python tools/cross_bench.py --profile c2:1024:1024
+                                                   ONE device leg and nothing else, for a kernel trace (rocprofv3 --kernel-trace --stats
+                                                   -- python tools/cross_bench.py --profile ...); prints the bytes the expansion
+                                                   and cbh_compact_pack_kernel write, to be divided by the trace's kernel times
+One JSON line per configuration on stdout."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from cerbos_amd import capi, cross, workloads  # noqa: E402
+from cerbos_amd.flatten import Flattener  # noqa: E402
+from cerbos_amd.lower.blob import lower_rule_table  # noqa: E402
+from cerbos_amd.policy.loader import policies_from_docs  # noqa: E402
+from cerbos_amd.ruletable.build import rule_table_from_policies  # noqa: E402
+
+NOW = 1_700_000_000_000_000_000
+
+
+class Flattened:
+    """the halves flattened ONCE, before any clock starts: cross.py asks its flattener for them on every call"""
+
+    def __init__(self, fl):
+        self.fl, self.h = fl, None
+
+    def flatten(self, inputs, default_policy_version="default", default_scope="", sort=True):
+        if self.h is None:
+            self.h = self.fl.flatten(inputs, default_policy_version, default_scope, sort=sort)
+        return self.h
+
+
+def stats(times, decisions):
+    t = np.sort(np.asarray(times))
+    return {"min": decisions / t[-1], "median": decisions / float(np.median(t)), "max": decisions / t[0], "reps": int(t.size)}
+
+
+def timed(table, reps, warmup, body):
+    out = []
+    for k in range(warmup + reps):
+        table.synchronize()
+        t0 = time.perf_counter()
+        keep = body()
+        table.synchronize()
+        dt = time.perf_counter() - t0
+        if keep is not None:
+            keep.close()
+        if k >= warmup:
+            out.append(dt)
+    return out
+
+
+def setup(name, n, m):
+    lt = lower_rule_table(rule_table_from_policies(policies_from_docs(getattr(workloads, name + "_policies")())))
+    ins = getattr(workloads, name + "_requests")(n + m, seed=17).to_inputs()
+    principals, resources, actions = [i["principal"] for i in ins[:n]], [i["resource"] for i in ins[n:]], list(ins[0]["actions"])
+    fl = Flattened(Flattener(lt))
+    table = capi.Table(lt.blob)
+    table.set_resident_streams(1)
+    return lt, table, fl, principals, resources, actions
+
+
+def host_leg(lt, table, fl, p, r, a):
+    def body():
+        cb = cross.cross_product_batch(fl, lt.columns, p, r, a)
+        db = table.upload(cb)
+        table.launch(db, now_ns=NOW)
+        table.download(db, want=())
+        return db
+    return body
+
+
+def device_leg(lt, table, fl, p, r, a):
+    def body():
+        db = cross.cross_product_upload(table, fl, lt.columns, p, r, a)
+        table.launch(db, now_ns=NOW)
+        table.download_allow_bits(db)
+        return db
+    return body
+
+
+def launch_alone(table, db, reps, warmup):
+    def body():
+        table.launch(db, now_ns=NOW)
+    return timed(table, reps, warmup, body)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--host-only", action="store_true")
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--configs", default="c2:1024:1024,c2:4096:1024,t:1024:1024,t:4096:1024")
+    ap.add_argument("--profile", default=None, metavar="NAME:N:M")
+    args = ap.parse_args()
+    if args.reps < 10:
+        ap.error("at least 10 timed repetitions")
+    capi.init(0)
+    if args.profile:
+        name, n, m = args.profile.split(":")
+        n, m = int(n), int(m)
+        lt, table, fl, p, r, a = setup(name, n, m)
+        db = device_leg(lt, table, fl, p, r, a)()
+        plan = table.plan(db)
+        ncol, nm, A = len(lt.columns), n * m, len(a)
+        narrow = bin(int(plan.split("narrow columns 0x")[1].split("]")[0], 16)).count("1") if "narrow columns" in plan else 0
+        print(json.dumps({"profile": args.profile, "plan": plan, "columns": ncol,
+                          "cbh_cross_expand_kernel_bytes_written": nm * (64 + 9 * ncol),
+                          "cbh_cross_actions_kernel_bytes_written": nm * A * 4,
+                          "cbh_compact_pack_kernel_bytes_written": nm * (16 + 4 * narrow),
+                          "cbh_allow_bits_kernel_bytes_written": (nm * A + 63) // 64 * 8}))
+        db.close()
+        table.close()
+        return
+    for cfg in args.configs.split(","):
+        name, n, m = cfg.split(":")
+        n, m = int(n), int(m)
+        lt, table, fl, p, r, a = setup(name, n, m)
+        decisions = n * m * len(a)
+        line = {"workload": name, "n": n, "m": m, "a": len(a), "decisions": decisions, "columns": len(lt.columns),
+                "unit": "decisions per second, end to end (min / median / max over the timed repetitions)"}
+        line["host_leg"] = stats(timed(table, args.reps, args.warmup, host_leg(lt, table, fl, p, r, a)), decisions)
+        hb = table.upload(cross.cross_product_batch(fl, lt.columns, p, r, a))
+        line["host_batch_plan"] = table.plan(hb)
+        line["host_batch_launch_alone"] = stats(launch_alone(table, hb, args.reps, args.warmup), decisions)
+        hb.close()
+        if not args.host_only:
+            line["device_leg"] = stats(timed(table, args.reps, args.warmup, device_leg(lt, table, fl, p, r, a)), decisions)
+            db = cross.cross_product_upload(table, fl, lt.columns, p, r, a)
+            line["device_batch_plan"] = table.plan(db)
+            line["device_batch_launch_alone"] = stats(launch_alone(table, db, args.reps, args.warmup), decisions)
+            db.close()
+            line["device_slowest_over_host_fastest"] = line["device_leg"]["min"] / line["host_leg"]["max"]
+        table.close()
+        print(json.dumps(line), flush=True)
+
+
+if __name__ == "__main__":
+    main()
