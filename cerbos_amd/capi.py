@@ -476,6 +476,7 @@ class Table:
             if rc != 2:
                 break
             ob = np.empty(int(need.value) + 64, dtype=np.uint8)
+        self.last_wire_info = {f[0]: getattr(info, f[0]) for f in CWireInfo._fields_}   # (summed / the largest over the call's slices)
         if rc == 1:
             raise HostFlattenerNeeded(load().cbh_last_error().decode("utf-8", "replace"))
         _check(rc)
@@ -542,6 +543,7 @@ class Table:
             if rc != 2:
                 break
             cap, n_cap = max(cap, int(need.value) + 64), max(n_cap, int(info.n_requests))
+        self.last_wire_info = {f[0]: getattr(info, f[0]) for f in CWireInfo._fields_}
         if rc == 1:
             raise HostFlattenerNeeded(load().cbh_last_error().decode("utf-8", "replace"))
         _check(rc)

@@ -108,7 +108,15 @@ static inline u32 cbh_wire_hash(P p, u32 n) {
 // ---- atomics (device scope); the host simulation runs its fibers on one thread -----------------------------------
 #ifdef CBH_HOSTSIM
 static inline u64 w_cas64(u64* p, u64 expect, u64 v) { const u64 o = *p; if (o == expect) *p = v; return o; }
-static inline u64 w_load64(const u64* p) { return *p; }
+// A test switch of the simulator (tests/hostsim hostsim_wire_stale_reads, off by default): every k-th w_load64 - of ANY caller: the
+// dictionary probe of w_intern_fn, the fill kernel's first-route claim, the route table's probe - reads EMPTY whatever the word
+// holds, the stale line a probe may see on the device.  All three follow the load with the same compare-and-swap, so the claim
+// behind a stale read is lost and the caller must go on with what the compare-and-swap returned.  cbh_sim_lost_claims counts the
+// DICTIONARY claims lost that way (CBH_SIM_LOST_CLAIM in w_intern_fn).  (Statics of the one translation unit that includes this
+// header in a simulator build - hostsim.cpp, or cbh_engine.hip against fakehip: each has its own switch.)
+static u32 cbh_sim_stale_every = 0, cbh_sim_stale_tick = 0, cbh_sim_lost_claims = 0;
+static inline u64 w_load64(const u64* p) { return (cbh_sim_stale_every && ++cbh_sim_stale_tick % cbh_sim_stale_every == 0u) ? 0 : *p; }
+#define CBH_SIM_LOST_CLAIM(prev) { if ((prev) != 0) ++cbh_sim_lost_claims; }
 static inline u32 w_load32(const u32* p) { return *p; }
 static inline u32 w_add32(u32* p, u32 v) { const u32 o = *p; *p += v; return o; }
 static inline void w_or32(u32* p, u32 v) { *p |= v; }
@@ -124,6 +132,7 @@ __device__ __forceinline__ u32 w_add32(CBH_G u32* p, u32 v) { return atomicAdd((
 __device__ __forceinline__ void w_or32(CBH_G u32* p, u32 v) { atomicOr((unsigned int*)p, v); }
 __device__ __forceinline__ void w_max32(CBH_G u32* p, u32 v) { atomicMax((unsigned int*)p, v); }
 __device__ __forceinline__ void w_min32(CBH_G u32* p, u32 v) { atomicMin((unsigned int*)p, v); }
+#define CBH_SIM_LOST_CLAIM(prev)
 #endif
 
 // The bytes a lane parses: MP is `const CBH_L u8*` - the fill kernel stages its wave's messages in LDS with one coalesced copy when
@@ -360,7 +369,7 @@ __device__ __attribute__((noinline)) u64 w_intern_fn(WTab t, MP m, u32 bias, u32
   u32 i = h & t.lix_mask;
   for (u32 n = 0; n < CBH_WIRE_MAX_PROBES; ++n, i = (i + 1u) & t.lix_mask) {
     u64 cur = w_load64(t.lix + i);
-    if (cur == 0) { const u64 prev = w_cas64(t.lix + i, 0, key); cur = prev == 0 ? key : prev; }
+    if (cur == 0) { const u64 prev = w_cas64(t.lix + i, 0, key); cur = prev == 0 ? key : prev; CBH_SIM_LOST_CLAIM(prev) }
     if (cur == key || ((cur >> 32) == (key >> 32) && w_bytes_eq(s, t.msg + (u32)cur, len))) {
       if (flag) {
         const u32 sh = (i & 3u) * 8u;

@@ -413,6 +413,16 @@ extern "C" int hostsim_wire_flatten(const void* blob, size_t len, const uint8_t*
   return 0;
 }
 
+// The header's own string hash (tests/test_string_interning.py pins its numpy restatement against it before searching collisions).
+extern "C" uint32_t hostsim_wire_hash(const uint8_t* bytes, uint32_t n) { return cbh_wire_hash(bytes, n); }
+// cbh_wire.h's test switch: every k-th w_load64 of any caller (dictionary probe, first-route claim, route table probe) reads EMPTY
+// (0: off).  Returns the DICTIONARY claims lost since the last call.
+extern "C" uint32_t hostsim_wire_stale_reads(uint32_t k) {
+  const uint32_t lost = cbh_sim_lost_claims;
+  cbh_sim_stale_every = k; cbh_sim_stale_tick = 0; cbh_sim_lost_claims = 0;
+  return lost;
+}
+
 // The request splitter (cbh_wire_req.h) on the simulator: n serialized CheckResourcesRequests (+ per-request engine AuxData, or
 // null) -> the CheckInputs of their resource entries, as cbh_wire_flatten_requests makes them on the device.  Returns the number of
 // inputs (the buffers are valid until the next call), -1 with *first_bad = the first malformed request.
