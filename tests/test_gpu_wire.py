@@ -206,3 +206,121 @@ def test_two_calls_in_flight_from_one_thread(total=40_000):
     with pytest.raises(capi.HostFlattenerNeeded, match="host flattener"):
         table.wire_check_pb_collect(t)
     table.close()
+
+
+def _request(principal, group):
+    return wire.encode_check_resources_request({"requestId": "r", "principal": principal,
+                                                "resources": [{"actions": i["actions"], "resource": i["resource"]} for i in group]})
+
+
+def _request_with_a_broken_second_entry(a, b, c):
+    """three resource entries; the second is malformed INSIDE - its resource's id claims more bytes than the resource holds - and
+    the request around it is sound"""
+    sound = _request(a["principal"], [a, dict(b, resource=dict(b["resource"], id="XXXXXXXX")), c])
+    at = sound.index(b"\x08XXXXXXXX")
+    return sound[:at] + b"\x7f" + sound[at + 1:]
+
+
+def small_shapes_body():
+    """One table, one replica, calls of 129, 65, 64, 63 and 1 messages in that order: 129 is two full waves and one lane of a third,
+    the smallest batch whose routes are grouped (C5 has several); every later call leases the page-locked block an earlier, larger
+    call gave back.  Each against the host road; a second cbh_wire_outputs on the same batch (its sizes are known) gives the first's
+    bytes; the road in one call gives them too.  Then a block leased at EXACTLY the size the call asks for (360 + tail + 9 n bytes
+    = the 64 KB of the block the calls before left): the outputs' offsets do not fit it and come back by copies."""
+    lt = lower_rule_table(rule_table_from_policies(policies_from_docs(workloads.c5_policies())))
+    inputs = workloads.c5_requests(n_requests=7_240).to_inputs()
+    msgs = [wire.encode_check_input(i) for i in inputs]
+    table, it = capi.Table(lt.blob), IngestTable(lt.blob)
+    flags = capi.F_WANT_DERIVED_ROLES
+    try:
+        for n in (129, 65, 64, 63, 1):
+            data, off = wire.pack_messages(msgs[:n])
+            hb = it.flatten_pb(data, off)
+            want_dev = table.check(hb, now_ns=NOW, flags=flags, device_order=True)
+            want_out, want_flags = it.assemble_pb(hb, want_dev, data, off)
+            db = table.wire_flatten(data, off)
+            assert (db.wire_info["n_routes"] > 1) == (n == 129), (n, db.wire_info)
+            table.launch(db, now_ns=NOW, flags=flags)
+            first = table.wire_outputs(db)
+            again = table.wire_outputs(db)
+            db.close()
+            one_call = table.wire_check_pb(data, off, now_ns=NOW, flags=flags)
+            for what, (out, oflags) in (("first", first), ("again", again), ("one call", one_call)):
+                assert out == want_out and np.array_equal(oflags[:n], want_flags[:n]), (n, what)
+        n, version = 7_240, "v" * 10
+        assert 360 + len(version) + 6 + 9 * n == 1 << 16
+        data, off = wire.pack_messages(msgs[:n])
+        hb = it.flatten_pb(data, off, default_policy_version=version)
+        want_dev = table.check(hb, now_ns=NOW, flags=flags, device_order=True)
+        want_out, want_flags = it.assemble_pb(hb, want_dev, data, off)
+        db = table.wire_flatten(data, off, default_policy_version=version)
+        table.launch(db, now_ns=NOW, flags=flags)
+        got = table.wire_outputs(db)
+        db.close()
+        assert got[0] == want_out and np.array_equal(got[1][:n], want_flags[:n])
+        # a malformed resource entry in a later request: the error names the request and which of its entries
+        p0 = inputs[0]["principal"]
+        with pytest.raises(capi.HipEngineError, match=r"malformed CheckResourcesRequest at index 2 \(resource entry 1\)"):
+            table.wire_check_requests_pb([_request(p0, inputs[:3]), _request(p0, []), _request_with_a_broken_second_entry(*inputs[3:6])], now_ns=NOW, flags=flags)
+        assert table.last_wire_info["first_bad"] == 2, table.last_wire_info
+    finally:
+        table.close()
+        it.close()
+
+
+def test_small_shapes_and_a_reused_block():
+    small_shapes_body()
+
+
+def single_message_slices_body():
+    """CBH_WIRE_SLICE_MIN=1 (the caller's process sets it): calls of 2 and 3 messages are cut into 2 and 3 slices of one message - the
+    chain of uploads, the bases from the predecessors' sizes - and give the bytes of the three calls; and the request road with a
+    request that has NO resource entries between two that have some: it gets no outputs, the others get theirs."""
+    lt = lower_rule_table(rule_table_from_policies(policies_from_docs(workloads.c5_policies())))
+    inputs = workloads.c5_requests(n_requests=6).to_inputs()
+    msgs = [wire.encode_check_input(i) for i in inputs]
+    table = capi.Table(lt.blob)
+    flags = capi.F_WANT_DERIVED_ROLES
+    try:
+        for n in (2, 3):
+            data, off = wire.pack_messages(msgs[:n])
+            db = table.wire_flatten(data, off)
+            table.launch(db, now_ns=NOW, flags=flags)
+            want, wflags = table.wire_outputs(db)
+            db.close()
+            got, gflags = table.wire_check_pb(data, off, now_ns=NOW, flags=flags)
+            assert got == want and list(gflags) == list(wflags), n
+
+        def request(group):
+            return _request(inputs[0]["principal"], group)
+        full = table.wire_check_requests_pb([request(inputs[:3]), request(inputs[3:])], now_ns=NOW, flags=flags, trail=True)
+        gap = table.wire_check_requests_pb([request(inputs[:3]), request([]), request(inputs[3:])], aux=[b"", None, b""], now_ns=NOW, flags=flags, trail=True)
+        assert [len(o) for o in gap[0]] == [3, 0, 3]
+        assert gap[0][0] == full[0][0] and gap[0][2] == full[0][1] and list(gap[1]) == list(full[1])
+        assert np.array_equal(gap[3][0], full[3][0]) and np.array_equal(gap[3][2], full[3][1]) and not gap[3][1].any()
+        # ... and a malformed second entry in the third request, which is a slice of its own here: first_bad counts the call's requests
+        # (the message counts the slice's, as it always has), the entry is named
+        with pytest.raises(capi.HipEngineError, match=r"malformed CheckResourcesRequest at index 0 \(resource entry 1\)"):
+            table.wire_check_requests_pb([request(inputs[:3]), request([]), _request_with_a_broken_second_entry(*inputs[3:6])], now_ns=NOW, flags=flags)
+        assert table.last_wire_info["first_bad"] == 2, table.last_wire_info
+    finally:
+        table.close()
+
+
+SLICE_ENVS = [{}, {"CBH_WIRE_LINK_STREAMS": "0", "CBH_TRACE": "1"}]   # (the second: every copy on the slice's own stream, the chain's events; a trace line per slice)
+
+
+@pytest.mark.parametrize("extra", SLICE_ENVS, ids=["link streams", "own streams, traced"])
+def test_slices_of_single_messages_and_a_request_without_entries(extra):
+    """(the switches are read once: a process of its own)"""
+    import os
+    import subprocess
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    sim = os.environ.get("CBH_TEST_SIM_ENGINE") == "1"   # (tests/conftest.py: the tier's bodies against the simulator build - the child too)
+    code = ("import sys; sys.path[:0] = [%r, %r]\nimport contextlib\nfrom sim_engine import sim_engine\nimport test_gpu_wire as w\n"
+            "with (sim_engine() if %r else contextlib.nullcontext()):\n    w.single_message_slices_body()\nprint('slices ok')\n" % (here, os.path.dirname(here), sim))
+    out = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, CBH_WIRE_SLICE_MIN="1", CBH_WIRE_SLICE_MIN_BYTES="1", **extra),
+                         capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and "slices ok" in out.stdout, out.stdout[-2000:] + out.stderr[-4000:]
+    assert ("[cbh] wire slice 2:" in out.stderr) == bool(extra), out.stderr[-2000:]

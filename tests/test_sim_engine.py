@@ -59,6 +59,17 @@ def test_trail_walk_tables(engine, name, n):
     t.test_walk_tables_by_input(name, n)
 
 
+def test_wire_small_shapes_and_a_reused_block(engine):
+    import test_gpu_wire as w
+    w.small_shapes_body()
+
+
+@pytest.mark.parametrize("extra", [0, 1], ids=["link streams", "own streams, traced"])
+def test_wire_slices_of_single_messages_and_a_request_without_entries(extra):
+    from test_gpu_wire import SLICE_ENVS
+    _in_own_process("import test_gpu_wire as w\nw.single_message_slices_body()\n", dict({"CBH_WIRE_SLICE_MIN": "1", "CBH_WIRE_SLICE_MIN_BYTES": "1"}, **SLICE_ENVS[extra]))
+
+
 def _in_own_process(body, env):
     """Switches the library reads once (static) need a process of their own."""
     import os

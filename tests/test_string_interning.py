@@ -37,8 +37,8 @@ named, every other test of the module passes under it):
   (c) `cur = key` after a lost compare-and-swap   test_lost_claims_on_emulator (nothing else loses a claim)
   (d) w_bytes_eq's tail mask one byte short       the ten of (a), test_length_limits_on_emulator, test_length_limits_on_simulator,
                                                   test_contended_claims_body_on_simulator
-  (e) `slots *= 4` without the statistics reset   cbh_engine.hip: test_regrowth_on_simulator, test_regrowth_in_slices_on_simulator; with n_host left
-      (cbh_engine.hip) / a stale n_host           stale in hostsim.cpp's own loop: test_regrowth_twin_on_emulator, test_lost_claims_on_emulator
+  (e) `slots *= 4` without the statistics reset   cbh_host_wire.h: test_regrowth_on_simulator, test_regrowth_in_slices_on_simulator; with n_host left
+      (cbh_host_wire.h wire_flatten_stages) / a stale n_host           stale in hostsim.cpp's own loop: test_regrowth_twin_on_emulator, test_lost_claims_on_emulator
       (hostsim.cpp's loop)
   (f) str_span's length mask 15 bits wide         test_length_limits_on_simulator
   (g) `len >= CBH_WIRE_MAX_STRLEN`                test_length_limits_on_emulator, test_length_limits_on_simulator
@@ -50,7 +50,7 @@ under the same mutants:
         test_varints_longer_than_they_need_to_be, test_mutated_messages_both_flatteners_agree; test_request_road.py
         test_requests_down_the_device_road_on_the_simulator[cr_case_03 | 06 | 07 | 08], test_every_request_s_audit_trail_beside_its_outputs;
         test_sim_engine.py test_request_road_service_cases, test_request_road_audit_trail_golden_store, test_the_roads_in_slices
-  (e)   hostsim.cpp's loop: test_wire_device.py test_fuzz_inputs[0 - 5]; cbh_engine.hip's loop: none of the 62"""
+  (e)   hostsim.cpp's loop: test_wire_device.py test_fuzz_inputs[0 - 5]; cbh_host_wire.h's loop: none of the 62"""
 import ctypes as C
 import os
 import subprocess
@@ -513,7 +513,7 @@ def host_road_outputs(capi, lt, inputs):
 
 
 def check_regrowth_on_library(capi, n=160, per=110):
-    """cbh_wire_flatten's retry loops (cbh_engine.hip): the dictionary quadrupled - twice -, the scan and the fill run again, the
+    """cbh_wire_flatten's retry loops (cbh_host_wire.h: wf_fill, wire_flatten_stages): the dictionary quadrupled - twice -, the scan and the fill run again, the
     routing kernels again behind them; then the same with a heap guess that is short as well.  The grouped order itself is not
     something the library hands out: what can be held against the host road's routing sort is the number of routes (wire_info's
     n_routes, as tests/test_gpu_wire.py does) and the answers in input order, byte for byte."""
