@@ -128,10 +128,12 @@ __device__ __forceinline__ void store_nt(CBH_G T* p, T v) {
 struct __attribute__((aligned(64))) TblDrx { u32 rm_lo, rm_hi, flags, cond, name, p0, p1, p2; LeafRec leaf; };
 
 // A cached attribute column for this lane: tag and the two value dwords (cbh_check_wave.h fill_column_cache).
+// PT: the cache's tags are known to be in the packed form (cbh_vm.h cached_tag) - the compact instantiations.
 struct FlatCol { u32 t, lo, hi; };
+template <bool PT = false>
 __device__ __forceinline__ FlatCol flat_col(const Ctx& c, u32 col, u32 req) {   // `col` wave-uniform
   FlatCol v;
-  v.t = cached_tag(c, col, req);
+  v.t = cached_tag<PT>(c, col, req);
   v.lo = c.cc[col * CBH_BLOCK + c.tid];
   v.hi = c.cc[(c.n_cached + col) * CBH_BLOCK + c.tid];
   return v;
@@ -142,20 +144,20 @@ __device__ __forceinline__ FlatCol flat_col(const Ctx& c, u32 col, u32 req) {   
 // for the shapes not listed here.  Returns bit 0 = satisfied, bit 1 = CEL error (counts as not satisfied),
 // bit 2 = undecided here (mixed numeric types, containers): the caller hands that lane to eval_cond_rec.
 // LISTS = false: the variant for tables closed over classes 1-4 and 6 (CBH_MF_FLAT_CLOSED), which never hold a membership leaf.
-template <bool LISTS = true>
+template <bool LISTS = true, bool PT = false>
 __device__ __forceinline__ u32 flat_leaf(const Ctx& c, const LeafRec& lr, u32 req, u32 pid) {
   const u32 a = lr.w >> 8;
   const u32 ka = (a >> 8) & 0xFu, op = a & 0xFFu;   // wave-uniform
   const bool want_eq = op == OP_EQ;
   switch (lr.pad) {
     case 1: {   // column ==/!= string or bool constant
-      const FlatCol x = flat_col(c, lr.a0, req);
+      const FlatCol x = flat_col<PT>(c, lr.a0, req);
       const bool err = x.t >= CBH_T_ABSENT;   // ABSENT (0xF0) or ERR (0xFF)
       const bool eq = x.t == lr.ctag && x.lo == lr.clo;   // other types are plainly unequal
       return err ? 2u : (u32)(eq == want_eq);
     }
     case 2: {   // column <op> double constant
-      const FlatCol x = flat_col(c, lr.a0, req);
+      const FlatCol x = flat_col<PT>(c, lr.a0, req);
       const bool err = x.t >= CBH_T_ABSENT;
       const bool dbl = x.t == CBH_T_DOUBLE, othernum = x.t == CBH_T_INT || x.t == CBH_T_UINT;
       const double p = as_f64((u64)x.lo | ((u64)x.hi << 32)), q = as_f64((u64)lr.clo | ((u64)lr.chi << 32));
@@ -168,7 +170,7 @@ __device__ __forceinline__ u32 flat_leaf(const Ctx& c, const LeafRec& lr, u32 re
       return (err || overload) ? 2u : slow ? 4u : r;
     }
     case 3: {   // column ==/!= column
-      const FlatCol x = flat_col(c, lr.a0, req), y = flat_col(c, lr.a1, req);
+      const FlatCol x = flat_col<PT>(c, lr.a0, req), y = flat_col<PT>(c, lr.a1, req);
       const bool err = x.t >= CBH_T_ABSENT || y.t >= CBH_T_ABSENT;
       const bool same = x.t == y.t;
       const bool scalar = x.t < CBH_T_LIST || x.t == CBH_T_TIMESTAMP || x.t == CBH_T_DURATION;
@@ -180,13 +182,13 @@ __device__ __forceinline__ u32 flat_leaf(const Ctx& c, const LeafRec& lr, u32 re
       return err ? 2u : slow ? 4u : (u32)(eq == want_eq);
     }
     case 4: {   // column ==/!= P.id (either order)
-      const FlatCol x = flat_col(c, ka == 3 ? lr.a0 : lr.a1, req);
+      const FlatCol x = flat_col<PT>(c, ka == 3 ? lr.a0 : lr.a1, req);
       const bool err = x.t >= CBH_T_ABSENT;
       const bool eq = x.t == CBH_T_STRING && x.lo == pid;
       return err ? 2u : (u32)(eq == want_eq);
     }
     case 6: {   // column in [at most three string constants]
-      const FlatCol x = flat_col(c, lr.a0, req);
+      const FlatCol x = flat_col<PT>(c, lr.a0, req);
       const bool err = x.t >= CBH_T_ABSENT;
       const bool found = x.t == CBH_T_STRING && (x.lo == lr.ctag || x.lo == lr.clo || x.lo == lr.chi);
       return err ? 2u : (u32)found;
@@ -194,12 +196,12 @@ __device__ __forceinline__ u32 flat_leaf(const Ctx& c, const LeafRec& lr, u32 re
     case 7:     // string constant in a list / among a map's keys the request brings
     case 8: {   // column in such a column
       if (!LISTS) return 4u;
-      const FlatCol h = flat_col(c, lr.a1, req);
+      const FlatCol h = flat_col<PT>(c, lr.a1, req);
       u32 nt = CBH_T_STRING, nlo = lr.clo;
       bool err = h.t >= CBH_T_ABSENT;
       if (lr.pad == 8u) {
         if (ka == 4u) nlo = pid;   // the principal's id
-        else { const FlatCol x = flat_col(c, lr.a0, req); nt = x.t; nlo = x.lo; err = err || x.t >= CBH_T_ABSENT; }
+        else { const FlatCol x = flat_col<PT>(c, lr.a0, req); nt = x.t; nlo = x.lo; err = err || x.t >= CBH_T_ABSENT; }
       }
       const bool is_map = h.t == CBH_T_MAP, cont = h.t == CBH_T_LIST || is_map;
       const u32 sel = h.hi >> 30, off = h.hi & 0x3FFFFFFFu, len = cont ? h.lo : 0u, stride = is_map ? 2u : 1u;
@@ -228,7 +230,7 @@ __device__ __forceinline__ u32 flat_leaf(const Ctx& c, const LeafRec& lr, u32 re
 // slot): the 4-bit ops in order, leaves from the strip, no tape reads and no divergent branch.  Same bookkeeping as
 // eval_leaf_tree (cbh_check_wave.h): a leaf behind the deciding one of its level is not evaluated by the reference
 // (check.go:697-749), so its error / "needs the full evaluator" flags do not count.  Returns flat_leaf's bits for the tree.
-template <bool LISTS = true>
+template <bool LISTS = true, bool PT = false>
 __device__ __forceinline__ u32 flat_tree(const Ctx& c, const LeafRec& desc, u32 req, u32 pid) {
   const u32 opw[4] = {desc.w, desc.a0, desc.ret, desc.ctag};   // wave-uniform
   bool live = true, last = false;
@@ -239,7 +241,7 @@ __device__ __forceinline__ u32 flat_tree(const Ctx& c, const LeafRec& desc, u32 
     if (op == 0) break;
     if (op == 1) {
       const LeafRec lr = uload_rec<LeafRec>(c.t.code, leaf++);
-      const u32 lv = flat_leaf<LISTS>(c, lr, req, pid);
+      const u32 lv = flat_leaf<LISTS, PT>(c, lr, req, pid);
       last = live && (lv & 1u) != 0;
       err |= live ? (lv & 2u) : 0u;
       slow |= live ? (lv & 4u) : 0u;
@@ -288,10 +290,12 @@ __device__ __forceinline__ u32 lv_of_code(u32 code) { return code == 3u ? 4u : c
 // lane's last column stays in registers (a class's leaves are laid out by column).  The answers are flat_leaf's, as 2-bit
 // outcomes: 0 false, 1 true, 2 CEL error, 3 needs the full evaluator.
 struct __attribute__((aligned(64))) Leaf4x4 { u32 w[16]; };
+template <bool PT>
 __device__ __forceinline__ void leaf_col(const Ctx& c, u32 w, u32 req, u32& curcol, FlatCol& x) {   // `w`, `curcol` wave-uniform
   const u32 col = (w >> 16) & 0xFFu;
-  if (col != curcol) { x = flat_col(c, col, req); curcol = col; }
+  if (col != curcol) { x = flat_col<PT>(c, col, req); curcol = col; }
 }
+template <bool PT>
 __device__ __forceinline__ u32 leaf_block_codes(const Ctx& c, const Leaf4x4& b, u32 req, u32 pid, u32& curcol, FlatCol& x) {
   const u32 cls = b.w[0] & 15u;   // the block's class
   u32 acc = 0;
@@ -299,7 +303,7 @@ __device__ __forceinline__ u32 leaf_block_codes(const Ctx& c, const Leaf4x4& b, 
 #pragma unroll
     for (u32 q = 0; q < 4; ++q) {
       const u32 w = b.w[4 * q];
-      leaf_col(c, w, req, curcol, x);
+      leaf_col<PT>(c, w, req, curcol, x);
       const bool ne = ((w >> 4) & 0xFFu) != OP_EQ;
       const bool eq = x.t == b.w[4 * q + 1] && x.lo == b.w[4 * q + 2];
       acc |= (x.t >= CBH_T_ABSENT ? 2u : (u32)(eq != ne)) << (2u * q);
@@ -308,7 +312,7 @@ __device__ __forceinline__ u32 leaf_block_codes(const Ctx& c, const Leaf4x4& b, 
 #pragma unroll
     for (u32 q = 0; q < 4; ++q) {
       const u32 w = b.w[4 * q], op = (w >> 4) & 0xFFu;
-      leaf_col(c, w, req, curcol, x);
+      leaf_col<PT>(c, w, req, curcol, x);
       const bool a_lt = op == OP_LT || op == OP_LE || op == OP_NE, a_eq = op == OP_EQ || op == OP_LE || op == OP_GE,
                  a_gt = op == OP_GT || op == OP_GE || op == OP_NE, a_un = op == OP_NE;   // (NaN: every ordering false, != true)
       const double p = as_f64((u64)x.lo | ((u64)x.hi << 32)), k = as_f64((u64)b.w[4 * q + 1] | ((u64)b.w[4 * q + 2] << 32));
@@ -323,7 +327,7 @@ __device__ __forceinline__ u32 leaf_block_codes(const Ctx& c, const Leaf4x4& b, 
 #pragma unroll
     for (u32 q = 0; q < 4; ++q) {
       const u32 w = b.w[4 * q];
-      leaf_col(c, w, req, curcol, x);
+      leaf_col<PT>(c, w, req, curcol, x);
       const bool found = x.t == CBH_T_STRING && (x.lo == b.w[4 * q + 1] || x.lo == b.w[4 * q + 2] || x.lo == b.w[4 * q + 3]);
       acc |= (x.t >= CBH_T_ABSENT ? 2u : (u32)found) << (2u * q);
     }
@@ -331,7 +335,7 @@ __device__ __forceinline__ u32 leaf_block_codes(const Ctx& c, const Leaf4x4& b, 
 #pragma unroll
     for (u32 q = 0; q < 4; ++q) {
       const u32 w = b.w[4 * q];
-      leaf_col(c, w, req, curcol, x);
+      leaf_col<PT>(c, w, req, curcol, x);
       const bool ne = ((w >> 4) & 0xFFu) != OP_EQ;
       acc |= (x.t >= CBH_T_ABSENT ? 2u : (u32)((x.t == CBH_T_STRING && x.lo == pid) != ne)) << (2u * q);
     }
@@ -339,8 +343,8 @@ __device__ __forceinline__ u32 leaf_block_codes(const Ctx& c, const Leaf4x4& b, 
 #pragma unroll
     for (u32 q = 0; q < 4; ++q) {
       const u32 w = b.w[4 * q];
-      leaf_col(c, w, req, curcol, x);
-      const FlatCol y = flat_col(c, (w >> 24) & 0xFFu, req);
+      leaf_col<PT>(c, w, req, curcol, x);
+      const FlatCol y = flat_col<PT>(c, (w >> 24) & 0xFFu, req);
       const bool ne = ((w >> 4) & 0xFFu) != OP_EQ;
       const bool same = x.t == y.t;
       const bool scalar = x.t < CBH_T_LIST || x.t == CBH_T_TIMESTAMP || x.t == CBH_T_DURATION;
@@ -356,6 +360,7 @@ __device__ __forceinline__ u32 leaf_block_codes(const Ctx& c, const Leaf4x4& b, 
 }
 // The blocks of `todo` (bit g = leaves 4g .. 4g + 3 of the pool at `recs`; wave-uniform) into `lvtab`, front to back; the next
 // block's record is in flight while this one is evaluated.
+template <bool PT>
 __device__ __forceinline__ void eval_leaf_blocks(const Ctx& c, const CBH_G u32* recs, u32 todo, u32 req, u32 pid, CBH_L u8* lvtab) {
   if (todo == 0) return;
   u32 curcol = CBH_NONE;
@@ -367,7 +372,7 @@ __device__ __forceinline__ void eval_leaf_blocks(const Ctx& c, const CBH_G u32* 
     const Leaf4x4 b = nxt;
     const u32 gn = todo ? (u32)__builtin_ctz(todo) : g;
     nxt = uload_rec<Leaf4x4>(recs, gn);
-    lvtab[g * CBH_BLOCK + c.tid] = (u8)leaf_block_codes(c, b, req, pid, curcol, cx);
+    lvtab[g * CBH_BLOCK + c.tid] = (u8)leaf_block_codes<PT>(c, b, req, pid, curcol, cx);
     g = gn;
   }
 }
@@ -436,7 +441,8 @@ __device__ __forceinline__ u64 load_u64g(const CBH_G u32* p) {   // 8-byte align
 // (not those of a role behind the one that allowed) have touched.  A bucket of a flat table is one resource policy's.
 // MEMO: the walk keeps the wave's last four condition outcomes (leafish_memo below) - the instantiation for tables WITH derived roles
 // (cbh_check_flat_kernel_dr): the memo's registers cost the plain kernel a wave of occupancy and C2 2 % for nothing.
-// COMPACT: the request record and the 32-bit value planes of a resident batch (cbh_vm.h BatchDev.creq / cval) instead of the wide arrays.
+// COMPACT: the request record, the 32-bit value planes and the tag planes of a resident batch (cbh_vm.h BatchDev.creq / cval / ctag) instead
+// of the wide arrays; the cache's tags are then in the packed form whatever the launch's flag says (the host sets it, and sizes the LDS).
 template <bool WITH_CALL, int MODE, bool EP = false, bool MEMO = false, bool COMPACT = false>
 __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c) {
   constexpr bool STAGED = MODE == 1;
@@ -470,8 +476,8 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c) {
   bool spec = false; u32 spec_ix = 0;
   if constexpr (COMPACT) {
     // ---- the compact form (cbh_vm.h BatchDev.creq): ONE 16-byte load brings everything the walk takes from the request words, the
-    // role ids and the action ids - the classes were looked up when the batch was uploaded.  First trip: the record and the tag
-    // bytes; second: the columns' copies and the chain's first scope.  No class table is read, none is staged in LDS, and the
+    // role ids and the action ids - the classes were looked up when the batch was uploaded.  First trip: the record; second:
+    // the columns' and the tags' copies (cc_fill_compact) and the chain's first scope.  No class table is read, none is staged in LDS, and the
     // prologue has no barrier of its own.
     const u32x4u rec = load_u32x4(b.creq + 4u * (size_t)req);
     pid = rec.x; kind = rec.y & 0xFFFFu; r_ver = rec.y >> 16;
@@ -504,7 +510,9 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c) {
   const u32 cls_i = threadIdx.x < t.K ? threadIdx.x : kmax;
   cls_a0 = (t.K ? t.action_class : (const CBH_G u8*)b.req_u32)[cls_i]; cls_r0 = (t.K ? t.role_class : (const CBH_G u8*)b.req_u32)[cls_i];
   }
-  const CcTags cct = cc_load_tags(c, b, NR, w0, wd);
+  CcTags cct;
+  if constexpr (COMPACT) { for (u32 g = 0; g < CBH_CACHE_COLS / 4; ++g) cct.w[g] = 0; } else cct = cc_load_tags(c, b, NR, w0, wd);   // (compact: the tags arrive as copies, cc_fill_compact)
+  const bool ptags = COMPACT || (c.flags & CBH_FI_PACKED_TAGS) != 0;   // the form of the cache's tags (CBH_CC_DWORDS)
   const u32 all = (1u << act_cnt) - 1u;
   // [depth][lane]: scope index at that depth of the lane's chain - in the dynamic LDS behind the column caches,
   // sized by the table's longest chain (a one-scope table pays 256 B per wave, not 4 KB: LDS sets the occupancy here)
@@ -512,7 +520,7 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c) {
   // A table of at most 256 scopes keeps them as bytes: a quarter of the footprint.
   const bool chain8 = t.n_scopes <= 256u;
   const u32 chain_dwords = chain8 ? max_depth * (CBH_BLOCK / 4u) : max_depth * CBH_BLOCK;
-  CBH_L u32* chain_si = (CBH_L u32*)cbh_dyn_lds + CBH_FLAT_WAVES * CBH_CC_DWORDS(c.n_cached, (c.flags & CBH_FI_PACKED_TAGS) != 0) + wave * chain_dwords;
+  CBH_L u32* chain_si = (CBH_L u32*)cbh_dyn_lds + CBH_FLAT_WAVES * CBH_CC_DWORDS(c.n_cached, ptags) + wave * chain_dwords;
   CBH_L u8* chain_si8 = (CBH_L u8*)chain_si;
   // actions and roles -> classes (CBH_SEC_ACTION_CLASS / CBH_SEC_ROLE_CLASS; 63 = a string no rule names).
   // A flat table has fewer than 32 classes per dimension and its masks mirror "any other string" (bit 63)
@@ -523,7 +531,7 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c) {
   // flight - a table of up to CBH_FLAT_LDS_STRINGS strings - so that the lookups below are LDS reads, not a third
   // dependent trip to memory.
   const bool cls_in_lds = t.K <= CBH_FLAT_LDS_STRINGS;
-  CBH_L u8* cls_lds = (CBH_L u8*)((CBH_L u32*)cbh_dyn_lds + CBH_FLAT_WAVES * (CBH_CC_DWORDS(c.n_cached, (c.flags & CBH_FI_PACKED_TAGS) != 0) + chain_dwords));   // [action classes K][role classes K]
+  CBH_L u8* cls_lds = (CBH_L u8*)((CBH_L u32*)cbh_dyn_lds + CBH_FLAT_WAVES * (CBH_CC_DWORDS(c.n_cached, ptags) + chain_dwords));   // [action classes K][role classes K]
   // second trip (wide form): the role ids (and, where the speculation missed, the action ids)
   u32 aid[4] = {0, 0, 0, 0}, rid[4] = {0, 0, 0, 0};
   if constexpr (!COMPACT) {
@@ -549,7 +557,7 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c) {
   CBH_L u32* ep_lds = (CBH_L u32*)(cls_lds + (cls_in_lds ? ((2u * t.K + 15u) & ~15u) : 0u) + (MODE == 2 ? CBH_FLAT_WAVES * CBH_SEG_LDS_BYTES : 0u)) + wave * max_depth * 2u * CBH_BLOCK;
   const bool want_ep = EP && (flags & CBH_F_WANT_EFFECTIVE_POLICIES) != 0 && o.eff_pol != nullptr;
   if (EP) { for (u32 d = 0; d < 2u * max_depth; ++d) ep_lds[d * CBH_BLOCK + c.tid] = 0; }
-  if constexpr (COMPACT) cc_fill_compact(c, b, NR, w0, wd, cct); else cc_fill(c, b, NR, w0, wd, cct);   // (behind every LDS store of this prologue)
+  if constexpr (COMPACT) cc_fill_compact(c, b, NR, w0, wd); else cc_fill(c, b, NR, w0, wd, cct);   // (behind every LDS store of this prologue)
   // ... and the chain's first scope (ruletable.go:848-882; per lane, reads the scope tables): its load goes out with the second trip
   const bool lenient = (flags & CBH_F_LENIENT_SCOPE_SEARCH) != 0;
   const u32 first = chain_first(t, r_scope, FLAG_RES, lenient);
@@ -596,8 +604,8 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c) {
   auto leafish = [&](u32 ref, u32 how, const LeafRec& lr, bool active) -> u32 {
     u32 lv = 4u;
     FLAT_DBG(const u64 e0 = __builtin_readcyclecounter(); ++dbg_evals;)
-    if (how == 1u) lv = flat_leaf<WITH_CALL>(c, lr, req, pid);
-    else if (how == 2u) lv = flat_tree<WITH_CALL>(c, lr, req, pid);
+    if (how == 1u) lv = flat_leaf<WITH_CALL, COMPACT>(c, lr, req, pid);
+    else if (how == 2u) lv = flat_tree<WITH_CALL, COMPACT>(c, lr, req, pid);
     FLAT_DBG(cyc_eval += (__builtin_readcyclecounter() - e0) * (u64)(wave_ballot(lv != 77u) != 0);)
     const bool slow = active && lv == 4u;
     if (WITH_CALL) {
@@ -732,7 +740,7 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c) {
               const u32 todo = ~blocks_done & ((1u << nblk) - 1u);
               if (todo) {
                 FLAT_DBG(const u64 l0 = __builtin_readcyclecounter();)
-                eval_leaf_blocks(c, pooled ? t.leafpool : blk + hd.off_leaves, todo, req, pid, lvtab);
+                eval_leaf_blocks<COMPACT>(c, pooled ? t.leafpool : blk + hd.off_leaves, todo, req, pid, lvtab);
                 blocks_done |= todo;
                 (void)wave_ballot(true);
                 FLAT_DBG(cyc_stage += (__builtin_readcyclecounter() - l0) * (u64)(wave_ballot(req != 0xdeadbeefu) != 0); dbg_visits += (u32)__builtin_popcount(todo);)
@@ -991,23 +999,38 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c) {
   const bool decided = first == CBH_NONE || !exists;   // nothing to evaluate: "NO_MATCH" (check.go:119-121, 168-170)
   const u32 pol_none = (u32)(decided ? CBH_P_NO_MATCH : (role_cnt ? CBH_P_RESOURCE : CBH_P_EMPTY)) << 28 | ((!decided && role_cnt) ? first : 0u);
   const u32 pol_hit = ((u32)CBH_P_RESOURCE << 28) | first;
-  u32 eff4 = 0, st4 = 0, pol[4], scp[4];
   const u32 st_ok = (t.flags & CBH_MF_TRACE_ALL) ? CBH_ST_WANTS_TRACE : CBH_ST_OK;   // outputs: this kernel cannot tell which inputs have any (cerbos_hip.h)
+  // Per action: did a role allow it, did any walk decide it, and the scope that walk was decided at (+ 1; 0 = none).  The deciding
+  // walk is the lowest role bit of the deciding kind, taken where it stands (bit 4r + k).  A table of one scope has no chain to
+  // read: a walk can only have been decided at the lane's first scope.
+  bool alw[4], won[4];
+  u32 sc1[4];
 #pragma unroll
   for (u32 k = 0; k < 4; ++k) {
-    const u32 ak = (allow >> k) & 0x1111u, dk = (deny >> k) & 0x1111u;
-    const u32 win = ak ? (ak & (0u - ak)) : (dk & (0u - dk));   // lowest role bit of the deciding kind
-    const u32 wb = win << k;                                     // back at its position 4r + k
-    u32 d = 0;
-    if (max_depth > 1u) d = ((dp0 & wb) ? 1u : 0u) | ((dp1 & wb) ? 2u : 0u) | ((dp2 & wb) ? 4u : 0u) | ((dp3 & wb) ? 8u : 0u);
-    pol[k] = win ? pol_hit : pol_none;
-    scp[k] = CBH_NONE;
-    if (win && k < act_cnt) scp[k] = chain8 ? (u32)chain_si8[d * CBH_BLOCK + c.tid] : chain_si[d * CBH_BLOCK + c.tid];
-    eff4 |= (u32)(ak ? CBH_EFFECT_ALLOW : CBH_EFFECT_DENY) << (8 * k);   // NO_MATCH -> DENY (check.go:451-453)
-    // an evaluation the reference would not have made - a role after the one that allowed - does not count
-    const u32 seen = ak ? (((ak & (0u - ak)) << 1) - 1u) : 0xFFFFu;
-    const u32 ek = (err >> k) & 0x1111u & seen, uk = (unsup >> k) & 0x1111u & seen;
-    st4 |= (u32)(uk ? CBH_ST_UNSUPPORTED : (ek ? CBH_ST_CEL_ERROR : st_ok)) << (8 * k);
+    const u32 ak = allow & (0x1111u << k), dk = deny & (0x1111u << k);
+    const u32 sel = ak ? ak : dk;
+    const u32 wb = sel & (0u - sel);
+    alw[k] = ak != 0; won[k] = sel != 0;
+    u32 s = first;
+    if (max_depth > 1u) {
+      const u32 d = ((dp0 & wb) ? 1u : 0u) | ((dp1 & wb) ? 2u : 0u) | ((dp2 & wb) ? 4u : 0u) | ((dp3 & wb) ? 8u : 0u);
+      s = chain8 ? (u32)chain_si8[d * CBH_BLOCK + c.tid] : chain_si[d * CBH_BLOCK + c.tid];
+    }
+    sc1[k] = (won[k] && k < act_cnt) ? s + 1u : 0u;
+  }
+  // The status.  An evaluation error or a condition outside the device subset is a few lanes of a few waves: a wave without one
+  // writes the constant and skips the bookkeeping of which evaluations the reference would have made.
+  u32 st4 = st_ok * 0x01010101u;
+  if (wave_ballot((err | unsup) != 0) != 0) {
+    st4 = 0;
+#pragma unroll
+    for (u32 k = 0; k < 4; ++k) {
+      const u32 ak = (allow >> k) & 0x1111u;
+      // an evaluation the reference would not have made - a role after the one that allowed - does not count
+      const u32 seen = ak ? (((ak & (0u - ak)) << 1) - 1u) : 0xFFFFu;
+      const u32 ek = (err >> k) & 0x1111u & seen, uk = (unsup >> k) & 0x1111u & seen;
+      st4 |= (u32)(uk ? CBH_ST_UNSUPPORTED : (ek ? CBH_ST_CEL_ERROR : st_ok)) << (8 * k);
+    }
   }
 
   if (EP && want_ep && valid) {   // ---- effective policies: what the walks the reference really makes have touched
@@ -1075,13 +1098,6 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c) {
     if (dr_unsup) st4 = 0x02020202u;
   }
 
-#ifdef CBH_PROFILE_CYCLES
-  if (flags & CBH_F_DEBUG_CYCLES) {   // policy / scope words <- phase cycles, wall-clock (100 MHz) start / end, visit counts
-    const u64 cyc4 = __builtin_readcyclecounter();
-    pol[0] = (u32)(cyc1 - cyc0); pol[1] = (u32)cyc_eval; pol[2] = (u32)(cyc3 - cyc2); pol[3] = (u32)cyc_stage; (void)cyc4;
-    scp[0] = (u32)rt0; scp[1] = (u32)__builtin_amdgcn_s_memrealtime(); scp[2] = dbg_rows | (dbg_evals << 16); scp[3] = dbg_rounds | (dbg_visits << 16);
-  }
-#endif
   // (compact form: only the stores need the offset - a load up here, inside a uniform branch, would be waited for in the prologue)
   if constexpr (COMPACT) { if (!(b.compact_info & CBH_CI_ACT4)) act_off = b.req_u32[(size_t)CBH_RQ_ACT_OFF * NR + req]; }
   const bool packed = valid && act_cnt == 4 && (act_off & 3u) == 0;
@@ -1091,10 +1107,13 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c) {
   struct u32x4 { u32 x, y, z, w; };
 #endif
   if (flags & CBH_FI_PACKED_RES) {   // the packed form (cbh_vm.h cbh_pk_word) in the policy array: one 16-byte store per request
-    const u32 pkb = cbh_pk_bits(t.n_scopes);
+    // ... formed from the fold's facts directly: the policy word is one of two per lane (cbh_pk_word's kind and id fields)
+    const u32 sh = 7u + cbh_pk_bits(t.n_scopes);
+    const u32 pk_hit = ((pol_hit >> 28) << 4) | ((pol_hit & 0x0FFFFFFFu) << 7), pk_none = ((pol_none >> 28) << 4) | ((pol_none & 0x0FFFFFFFu) << 7);
     u32 pw[4];
 #pragma unroll
-    for (u32 k = 0; k < 4; ++k) pw[k] = cbh_pk_word((eff4 >> (8 * k)) & 0xFFu, (st4 >> (8 * k)) & 0xFFu, pol[k], scp[k], pkb);
+    for (u32 k = 0; k < 4; ++k)   // NO_MATCH -> DENY (check.go:451-453)
+      pw[k] = (u32)(alw[k] ? CBH_EFFECT_ALLOW : CBH_EFFECT_DENY) | (((st4 >> (8 * k)) & 0xFFu) << 2) | (won[k] ? pk_hit : pk_none) | (sc1[k] << sh);
     if (packed) {
       if (o.edr) store_nt(o.edr + req, edr);
       u32x4 v; v.x = pw[0]; v.y = pw[1]; v.z = pw[2]; v.w = pw[3];
@@ -1104,21 +1123,37 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c) {
 #pragma unroll
       for (u32 k = 0; k < 4; ++k) if (k < act_cnt) o.policy[act_off + k] = pw[k];
     }
-  } else if (packed) {
-    if (o.edr) store_nt(o.edr + req, edr);
-    store_nt((CBH_G u32*)(o.effect + act_off), eff4);
-    if (o.status) store_nt((CBH_G u32*)(o.status + act_off), st4);
-    if (o.policy) { u32x4 v; v.x = pol[0]; v.y = pol[1]; v.z = pol[2]; v.w = pol[3]; store_nt((CBH_G u32x4*)(o.policy + act_off), v); }
-    if (o.scope) { u32x4 v; v.x = scp[0]; v.y = scp[1]; v.z = scp[2]; v.w = scp[3]; store_nt((CBH_G u32x4*)(o.scope + act_off), v); }
-  } else if (valid) {
-    if (o.edr) o.edr[req] = edr;
+  } else {   // the wide form's words, from the same facts
+    u32 eff4 = 0, pol[4], scp[4];
 #pragma unroll
     for (u32 k = 0; k < 4; ++k) {
-      if (k < act_cnt) {
-        o.effect[act_off + k] = (u8)((eff4 >> (8 * k)) & 0xFFu);
-        if (o.status) o.status[act_off + k] = (u8)((st4 >> (8 * k)) & 0xFFu);
-        if (o.policy) o.policy[act_off + k] = pol[k];
-        if (o.scope) o.scope[act_off + k] = scp[k];
+      eff4 |= (u32)(alw[k] ? CBH_EFFECT_ALLOW : CBH_EFFECT_DENY) << (8 * k);   // NO_MATCH -> DENY (check.go:451-453)
+      pol[k] = won[k] ? pol_hit : pol_none;
+      scp[k] = sc1[k] - 1u;   // (0 -> CBH_NONE)
+    }
+#ifdef CBH_PROFILE_CYCLES
+    if (flags & CBH_F_DEBUG_CYCLES) {   // policy / scope words <- phase cycles, wall-clock (100 MHz) start / end, visit counts
+      const u64 cyc4 = __builtin_readcyclecounter();
+      pol[0] = (u32)(cyc1 - cyc0); pol[1] = (u32)cyc_eval; pol[2] = (u32)(cyc3 - cyc2); pol[3] = (u32)cyc_stage; (void)cyc4;
+      scp[0] = (u32)rt0; scp[1] = (u32)__builtin_amdgcn_s_memrealtime(); scp[2] = dbg_rows | (dbg_evals << 16); scp[3] = dbg_rounds | (dbg_visits << 16);
+    }
+#endif
+    if (packed) {
+      if (o.edr) store_nt(o.edr + req, edr);
+      store_nt((CBH_G u32*)(o.effect + act_off), eff4);
+      if (o.status) store_nt((CBH_G u32*)(o.status + act_off), st4);
+      if (o.policy) { u32x4 v; v.x = pol[0]; v.y = pol[1]; v.z = pol[2]; v.w = pol[3]; store_nt((CBH_G u32x4*)(o.policy + act_off), v); }
+      if (o.scope) { u32x4 v; v.x = scp[0]; v.y = scp[1]; v.z = scp[2]; v.w = scp[3]; store_nt((CBH_G u32x4*)(o.scope + act_off), v); }
+    } else if (valid) {
+      if (o.edr) o.edr[req] = edr;
+#pragma unroll
+      for (u32 k = 0; k < 4; ++k) {
+        if (k < act_cnt) {
+          o.effect[act_off + k] = (u8)((eff4 >> (8 * k)) & 0xFFu);
+          if (o.status) o.status[act_off + k] = (u8)((st4 >> (8 * k)) & 0xFFu);
+          if (o.policy) o.policy[act_off + k] = pol[k];
+          if (o.scope) o.scope[act_off + k] = scp[k];
+        }
       }
     }
   }
@@ -1130,10 +1165,12 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c) {
 #define CBH_FLAT_ATTRS(MINW)
 #endif
 // each wave of the group owns its slice of the column cache (CBH_CC_DWORDS)
-#define CBH_FLAT_CTX(a, ka)                                                                                                       \
+#define CBH_FLAT_CTX_(a, ka, PT)                                                                                                 \
   const u32 ncc = cached_columns(&a);                                                                                             \
   Ctx c{a.t, a.b, a.now_ns, a.flags, threadIdx.x % CBH_BLOCK, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,  \
-        (CBH_L u32*)cbh_dyn_lds + (threadIdx.x / CBH_BLOCK) * CBH_CC_DWORDS(ncc, (a.flags & CBH_FI_PACKED_TAGS) != 0), ncc, ka}
+        (CBH_L u32*)cbh_dyn_lds + (threadIdx.x / CBH_BLOCK) * CBH_CC_DWORDS(ncc, (PT)), ncc, ka}
+#define CBH_FLAT_CTX(a, ka) CBH_FLAT_CTX_(a, ka, (a.flags & CBH_FI_PACKED_TAGS) != 0)
+#define CBH_FLAT_CTX_C(a, ka) CBH_FLAT_CTX_(a, ka, true)   /* the compact instantiations: always the packed form */
 // batches of plain scalars (no int / uint / list / map attribute values): no call, ~64 VGPRs, 7-8 waves per SIMD
 __global__ CBH_FLAT_ATTRS(7) void cbh_check_flat_kernel(const KernelArgs a, const KernelArgs* __restrict__ ka) {
   CBH_FLAT_CTX(a, ka);
@@ -1173,15 +1210,15 @@ __global__ CBH_FLAT_ATTRS(3) void cbh_check_flat_kernel_any_masks(const KernelAr
 // registers, not by the bytes they read.  So does cbh_check_flat_kernel_dr: at its 72 registers (seven waves) the compact prologue
 // spilled two of them to scratch, and C3 is bound by instructions.
 __global__ CBH_FLAT_ATTRS(7) void cbh_check_flat_kernel_c(const KernelArgs a, const KernelArgs* __restrict__ ka) {
-  CBH_FLAT_CTX(a, ka);
+  CBH_FLAT_CTX_C(a, ka);
   flat_body<false, 0, false, false, true>(a, c);
 }
 __global__ CBH_FLAT_ATTRS(5) void cbh_check_flat_kernel_staged_c(const KernelArgs a, const KernelArgs* __restrict__ ka) {
-  CBH_FLAT_CTX(a, ka);
+  CBH_FLAT_CTX_C(a, ka);
   flat_body<false, 1, false, false, true>(a, c);
 }
 __global__ CBH_FLAT_ATTRS(4) void cbh_check_flat_kernel_masks_c(const KernelArgs a, const KernelArgs* __restrict__ ka) {
-  CBH_FLAT_CTX(a, ka);
+  CBH_FLAT_CTX_C(a, ka);
   flat_body<false, 2, false, false, true>(a, c);
 }
 // cbh_check_batch_trail on a flat table: the same six walks with the effective policies kept (flat_body EP)
@@ -1210,6 +1247,7 @@ __global__ __launch_bounds__(256) void cbh_unpack_results_kernel(PkUnpackArgs a)
 struct CompactArgs {
   const CBH_G u32* req_u32; const CBH_G u32* roles; const CBH_G u32* tuple_action; const CBH_G u64* col_val;
   const CBH_G u8* action_class; const CBH_G u8* role_class;
+  const CBH_G u8* col_tag; CBH_G u32* ctag;   // ctag: [(n_cached + 3) / 4][n_requests], four columns' tag bytes to a dword
   CBH_G u32* creq; CBH_G u32* cval; CBH_G u32* info;   // info[0]: bit k = column k has a high word, CBH_CI_MISFIT, CBH_CI_ACT4 INVERTED (some request is not aligned)
   u32 n_requests, n_cached, K, narrow;
 };
@@ -1255,11 +1293,20 @@ __global__ __launch_bounds__(256) void cbh_compact_pack_kernel(CompactArgs a) {
   u32 plane = 0;
   for (u32 k = 0; k < a.n_cached; ++k)
     if ((a.narrow >> k) & 1u) { a.cval[plane * NR + r] = (u32)a.col_val[k * NR + r]; ++plane; }
+  for (u32 g = 0; 4u * g < a.n_cached; ++g) {   // (a column beyond the last: a zero byte)
+    u32 w = 0;
+    for (u32 j = 0; j < 4u && 4u * g + j < a.n_cached; ++j) w |= (u32)a.col_tag[(4u * g + j) * NR + r] << (8u * j);
+    a.ctag[g * NR + r] = w;
+  }
 }
 // the compact instantiation of a flat kernel, or null where it has none (the variants with the evaluator call, the derived-role variant, the trail's)
 static inline cbh_check_kernel_fn cbh_flat_compact_variant(cbh_check_kernel_fn fn) {
   return fn == cbh_check_flat_kernel ? cbh_check_flat_kernel_c
        : fn == cbh_check_flat_kernel_staged ? cbh_check_flat_kernel_staged_c : fn == cbh_check_flat_kernel_masks ? cbh_check_flat_kernel_masks_c : nullptr;
+}
+// ... whose column cache always keeps its tags in the packed form (cbh_vm.h CBH_CC_DWORDS): the launch is sized for it
+static inline bool cbh_is_flat_compact_kernel(cbh_check_kernel_fn fn) {
+  return fn == cbh_check_flat_kernel_c || fn == cbh_check_flat_kernel_staged_c || fn == cbh_check_flat_kernel_masks_c;
 }
 #define CBH_FLAT_STAGE_MIN 32u
 // the mask walk decides a table that has segments and long buckets (CBH_FLAT_MASKS=0: never, =1: whatever the buckets' length - tests, A/B)

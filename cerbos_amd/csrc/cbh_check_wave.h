@@ -488,41 +488,32 @@ __device__ __forceinline__ void cc_fill(const Ctx& c, const BatchDev& b, u32 NR,
   }
 }
 
-// cc_fill for the compact form (cbh_vm.h BatchDev.cval): a column with a 32-bit plane issues ONE copy, of its low words (lane stride
-// 4), and its high plane in LDS is filled with zeros by a plain store - issued, like the packed tags, before any asynchronous copy
-// (an LDS access behind the copies waits for all of them).  The other columns are copied from col_val as in cc_fill.  The cache's
-// readers (flat_leaf, flat_tree, cached_tag) see the same three planes either way.
-__device__ __forceinline__ void cc_fill_compact(const Ctx& c, const BatchDev& b, u32 NR, u32 req0, u32 d, const CcTags& t) {
-  const bool packed = (c.flags & CBH_FI_PACKED_TAGS) != 0;
+// cc_fill for the compact form (cbh_vm.h BatchDev.cval / ctag): a column with a 32-bit plane issues ONE copy, of its low words (lane
+// stride 4), and its high plane in LDS is filled with zeros by a plain store - issued before any asynchronous copy (an LDS access
+// behind the copies waits for all of them).  The other columns are copied from col_val as in cc_fill.  The tags: ONE copy per group of
+// four columns, of the lane's dword of the batch's `ctag` plane, straight into the cache's packed tag plane - nothing through a
+// register, no byte position per lane.  A compact launch always has the packed form of the cache (the host sets CBH_FI_PACKED_TAGS
+// and sizes the LDS for it: cbh_host_resident.h launch_plan), so every reader of the cache sees what cc_fill would have left there.
+__device__ __forceinline__ void cc_fill_compact(const Ctx& c, const BatchDev& b, u32 NR, u32 req0, u32 d) {
   const u32 narrow = b.compact_info & CBH_CI_NARROW_MASK;   // uniform
   CBH_L u32* tags = c.cc + 2u * c.n_cached * CBH_BLOCK;
-  if (packed) {
-#pragma unroll
-    for (u32 g = 0; g < CBH_CACHE_COLS / 4; ++g) if (4u * g < c.n_cached) tags[g * CBH_BLOCK + c.tid] = t.w[g];
-  }
   for (u32 k = 0; k < c.n_cached; ++k) if ((narrow >> k) & 1u) c.cc[(c.n_cached + k) * CBH_BLOCK + c.tid] = 0u;
   const u32 d4 = d * 4u, d8 = d * 8u;
+  for (u32 g = 0; 4u * g < c.n_cached; ++g) {
+    const CBH_G char* tb = (const CBH_G char*)(b.ctag + ((size_t)g * NR + req0));   // uniform
+    lds_dma_dword(tb + d4, tags + g * CBH_BLOCK, c.tid);
+  }
   u32 plane = 0;   // narrow planes in front of column k (uniform)
   for (u32 k = 0; k < c.n_cached; ++k) {
-    const size_t u = (size_t)k * NR + req0;   // uniform
     if ((narrow >> k) & 1u) {
       const CBH_G char* vb = (const CBH_G char*)(b.cval + ((size_t)plane * NR + req0));
       lds_dma_dword(vb + d4, c.cc + k * CBH_BLOCK, c.tid);
       ++plane;
     } else {
-      const CBH_G char* vb = (const CBH_G char*)(b.col_val + u);
+      const CBH_G char* vb = (const CBH_G char*)(b.col_val + ((size_t)k * NR + req0));
       const CBH_G char* vb4 = vb + 4;
       lds_dma_dword(vb + d8, c.cc + k * CBH_BLOCK, c.tid);
       lds_dma_dword(vb4 + d8, c.cc + (c.n_cached + k) * CBH_BLOCK, c.tid);
-    }
-    if (!packed) {   // (as cc_fill)
-      const u32 sh = (u32)u & 3u;
-#ifndef CBH_HOSTSIM
-      const CBH_G char* tb = (const CBH_G char*)(b.col_tag + (u - sh));
-      lds_dma_dword(tb + ((d + sh) & ~3u), c.cc + (2 * c.n_cached + k) * CBH_BLOCK, c.tid);
-#else
-      c.cc[(2 * c.n_cached + k) * CBH_BLOCK + c.tid] = (u32)b.col_tag[u + d] << (((d + sh) & 3u) * 8u);
-#endif
     }
   }
 }

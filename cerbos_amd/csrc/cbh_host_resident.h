@@ -85,7 +85,7 @@ static int validate_batch(const cbh_table* t, const cbh_batch* in, BatchShape& s
 }
 
 // The compact form of a batch the flat kernels can decide (cbh_vm.h BatchDev.creq / cval), derived on the batch's stream from the wide
-// arrays already enqueued: the scan's verdict crosses to the host (one word), then the records and the 32-bit planes are written.  A
+// arrays already enqueued: the scan's verdict crosses to the host (one word), then the records, the 32-bit planes and the tag planes are written.  A
 // batch with a field that does not fit the record keeps the wide form; so does every batch under CBH_COMPACT_INPUTS=0 (measurement aid).
 static bool compact_inputs_on() { static const bool on = env_int("CBH_COMPACT_INPUTS", 1) != 0; return on; }
 static int batch_compact(cbh_device_batch* b, hipStream_t s) {
@@ -93,7 +93,7 @@ static int batch_compact(cbh_device_batch* b, hipStream_t s) {
   BatchDev& d = b->dev;
   if (!compact_inputs_on() || !(dev.flags & CBH_MF_FLAT) || b->max_actions > 4 || b->max_roles > 4 || !d.n_requests) return 0;
   CompactArgs ca{};
-  ca.req_u32 = d.req_u32; ca.roles = d.roles; ca.tuple_action = d.tuple_action; ca.col_val = d.col_val;
+  ca.req_u32 = d.req_u32; ca.roles = d.roles; ca.tuple_action = d.tuple_action; ca.col_val = d.col_val; ca.col_tag = d.col_tag;
   ca.action_class = dev.action_class; ca.role_class = dev.role_class; ca.K = dev.K;
   ca.n_requests = d.n_requests; ca.n_cached = d.n_columns < CBH_CACHE_COLS ? d.n_columns : CBH_CACHE_COLS;
   if (dalloc(b, ca.info, 1) != 0) return -1;
@@ -105,10 +105,11 @@ static int batch_compact(cbh_device_batch* b, hipStream_t s) {
   HIPCHK(hipStreamSynchronize(s));
   if (info & CBH_CI_MISFIT) return 0;
   ca.narrow = ~info & ((1u << ca.n_cached) - 1u) & CBH_CI_NARROW_MASK;
-  if (dalloc(b, ca.creq, (size_t)4 * d.n_requests) != 0 || dalloc(b, ca.cval, (size_t)__builtin_popcount(ca.narrow) * d.n_requests) != 0) return -1;
+  if (dalloc(b, ca.creq, (size_t)4 * d.n_requests) != 0 || dalloc(b, ca.cval, (size_t)__builtin_popcount(ca.narrow) * d.n_requests) != 0 ||
+      dalloc(b, ca.ctag, (size_t)((ca.n_cached + 3u) / 4u) * d.n_requests) != 0) return -1;
   hipLaunchKernelGGL(cbh_compact_pack_kernel, grid, dim3(256), 0, s, ca);
   HIPCHK(hipGetLastError());
-  d.creq = ca.creq; d.cval = ca.cval; d.compact_info = ca.narrow | ((info & CBH_CI_ACT4) ? 0u : CBH_CI_ACT4);
+  d.creq = ca.creq; d.cval = ca.cval; d.ctag = ca.ctag; d.compact_info = ca.narrow | ((info & CBH_CI_ACT4) ? 0u : CBH_CI_ACT4);
   b->compact = true;
   return 0;
 }
@@ -360,7 +361,7 @@ static void launch_plan(const CbhPlan& pl, const TableDev& dev, KernelArgs ka, c
   // where it lets a CU hold more workgroups of this kernel
   auto go = [&](cbh_check_kernel_fn fn, u32 grid, u32 threads, auto lds_of, const KernelArgs& a0, bool last) {
     const size_t wide = lds_of(false), packed = lds_of(true);
-    const bool use_packed = packed_tags_pay(fn, threads, wide, packed);
+    const bool use_packed = cbh_is_flat_compact_kernel(fn) || packed_tags_pay(fn, threads, wide, packed);   // (a compact instantiation has no other form)
     const size_t lds = use_packed ? packed : wide;
     KernelArgs a = a0;
     if (use_packed) a.flags |= CBH_FI_PACKED_TAGS;
@@ -422,8 +423,12 @@ static bool pk_fits(const TableDev& dev) {
 }
 
 // Does this launch read the batch's compact form?  A flat kernel that has a compact instantiation (not: the variants with the
-// evaluator call, the trail's kernels), and not a cycle-count launch.
+// evaluator call, the trail's kernels), and not a cycle-count launch - except in the profiling build, whose cycle counts are wanted
+// of the kernel the product launches (tools/gpu_cycles_flat.py).
 static bool launch_is_compact(const cbh_device_batch* b, const CbhPlan& pl, u32 eval_flags) {
+#ifdef CBH_PROFILE_CYCLES
+  eval_flags &= ~(u32)CBH_F_DEBUG_CYCLES;
+#endif
   return b->compact && pl.kind == 1 && !(eval_flags & CBH_F_DEBUG_CYCLES) && cbh_flat_compact_variant(pl.kernel) != nullptr;
 }
 

@@ -99,6 +99,7 @@ struct BatchDev {
   // bit CBH_CI_ACT4 = every request has ACT_OFF = 4 * request and ACT_CNT = 4.  creq = the request records, or null.
   u32 compact_info;
   const CBH_G u32* creq; const CBH_G u32* cval;   // [n_requests][4]; [narrow columns, in column order][n_requests]
+  const CBH_G u32* ctag;                           // [(cached columns + 3) / 4][n_requests]: column c's tag = byte c & 3 of plane c >> 2
 };
 // The compact form of a resident batch's inputs, derived on the device from the wide arrays when the batch is uploaded
 // (cbh_compact_scan_kernel / cbh_compact_pack_kernel, cbh_check_flat.h) and read by the flat kernels' compact instantiations.
@@ -110,7 +111,9 @@ struct BatchDev {
 // The classes are what the wide prologue computes from the ids and the table's two class tables, clamps included (31 = a string no
 // rule names, or an action / role the request does not have): a resident batch is bound to one immutable table image.
 // A cached column whose values' high words are zero in every request of the batch has a plane of its low words in `cval`; the
-// others are read from col_val.  Tags stay as bytes in col_tag.
+// others are read from col_val.  The tags of the cached columns are gathered four to a dword per request in `ctag` (a byte of a
+// column beyond the last is zero): a compact launch copies one dword per lane and group of four columns into the cache's packed
+// tag planes (CBH_CC_DWORDS) and never reads col_tag - a column's byte then sits at a position the code knows when it is compiled.
 #define CBH_CI_NARROW_MASK 0xFFFFu   /* (one bit per cached column: a static_assert next to CBH_CACHE_COLS ties the two) */
 #define CBH_CI_ACT4 0x10000u
 #define CBH_CI_MISFIT 0x20000u   /* (the scan's verdict only, never in BatchDev: a field does not fit the record) */
@@ -1270,9 +1273,12 @@ __device__ __forceinline__ int fast_compare(const Ctx& c, u32 op, Val x, Val y) 
   return -2;
 }
 
-// the tag of a cached column (`col` wave-uniform): the lane's byte of its dword in either form of the cache (CBH_CC_DWORDS)
+// the tag of a cached column (`col` wave-uniform): the lane's byte of its dword in either form of the cache (CBH_CC_DWORDS).
+// PACKED: the instantiation knows the form is the packed one (a compact launch: cbh_check_wave.h cc_fill_compact) - the byte's
+// position is the column's alone, a field extract at a uniform shift; else the launch's flag says which form it is.
+template <bool PACKED = false>
 __device__ __forceinline__ u32 cached_tag(const Ctx& c, u32 col, u32 req) {
-  const bool packed = (c.flags & CBH_FI_PACKED_TAGS) != 0;
+  const bool packed = PACKED || (c.flags & CBH_FI_PACKED_TAGS) != 0;
   const u32 tw = c.cc[(2u * c.n_cached + (packed ? col >> 2 : col)) * CBH_BLOCK + c.tid];
   const u32 byte = packed ? (col & 3u) : (u32)(((size_t)col * c.b.n_requests + req) & 3u);
   return (tw >> (byte * 8u)) & 0xFFu;
