@@ -38,6 +38,7 @@ EXPORTED_SYMBOLS = [
     "cbh_wire_flatten_requests", "cbh_wire_check_requests_pb", "cbh_wire_check_requests_trail_pb", "cbh_batch_set_trail", "cbh_trail_download",
     "cbh_table_num_policies", "cbh_table_policy_key", "cbh_check_batch_trail",
     "cbh_batch_upload_cross", "cbh_result_download_allow_bits",
+    "cbh_cross_upload", "cbh_cross_check", "cbh_cross_describe", "cbh_cross_release",
 ]
 
 
@@ -200,6 +201,15 @@ def load():
     lib.cbh_batch_upload_cross.restype = i32
     lib.cbh_result_download_allow_bits.argtypes = [vp, vp, vp, C.c_size_t]
     lib.cbh_result_download_allow_bits.restype = i32
+    if hasattr(lib, "cbh_cross_upload"):   # (a library of an earlier round in a same-box A/B: tests/test_abi.py is what insists on every symbol)
+        lib.cbh_cross_upload.argtypes = [vp, u32, C.POINTER(CBatch), C.POINTER(CCross), C.POINTER(vp)]
+        lib.cbh_cross_upload.restype = i32
+        lib.cbh_cross_check.argtypes = [vp, vp, C.POINTER(CParams), u32, u32, vp, vp, C.c_size_t]
+        lib.cbh_cross_check.restype = i32
+        lib.cbh_cross_describe.argtypes = [vp, vp, C.POINTER(CParams)]
+        lib.cbh_cross_describe.restype = C.c_char_p
+        lib.cbh_cross_release.argtypes = [vp]
+        lib.cbh_cross_release.restype = None
     _lib = lib
     return lib
 
@@ -431,6 +441,25 @@ class Table:
         nm = int(n_principals) * int(n_resources)
         return DeviceBatch(self, h, nm * int(act.size), nm)
 
+    def cross_upload(self, halves_batch, n_principals, n_resources, action_ids, p_order=None, r_order=None, device_index=0):
+        """``cbh_cross_upload``: the same arguments as ``upload_cross``, but nothing is materialised - the device keeps the
+        ``n_principals`` + ``n_resources`` rows and ``CrossSet.check`` decides tiles of resources straight from them.  Returns the
+        ``CrossSet``, or None where the set has no direct form (return value 1: take ``upload_cross``, which gives the same answers)."""
+        cb = make_cbatch(halves_batch, self.num_columns)
+        act = np.ascontiguousarray(action_ids, dtype=np.uint32)
+        po = None if p_order is None else np.ascontiguousarray(p_order, dtype=np.uint32)
+        ro = None if r_order is None else np.ascontiguousarray(r_order, dtype=np.uint32)
+        if (po is not None and po.size != n_principals) or (ro is not None and ro.size != n_resources):
+            raise ValueError("p_order / r_order must have one entry per principal / resource")
+        x = CCross(n_principals, n_resources, act.size, act.ctypes.data if act.size else None,
+                   po.ctypes.data if po is not None and po.size else None, ro.ctypes.data if ro is not None and ro.size else None)
+        h = C.c_void_p()
+        rc = load().cbh_cross_upload(self.h, device_index, C.byref(cb), C.byref(x), C.byref(h))
+        if rc == 1:
+            return None
+        _check(rc)
+        return CrossSet(self, h, int(n_principals), int(n_resources), int(act.size))
+
     def download_allow_bits(self, dbatch, into=None):
         """``cbh_result_download_allow_bits`` -> uint64[(n_tuples + 63) // 64]: bit k = tuple k (device order) of the last
         ``launch`` is EFFECT_ALLOW.  ``into``: a uint64 array to reuse (page-locked: ``pinned_empty``)."""
@@ -649,6 +678,60 @@ class DeviceBatch:
     def close(self):
         if self.h:
             load().cbh_batch_release(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DirectFormUnavailable(RuntimeError):
+    """cbh_cross_check returned 1: these flags choose a plan without a direct form (strict evaluation, the trail) - decide the
+    materialised product (``Table.upload_cross``) instead: same answers, other road."""
+
+
+class CrossSet:
+    """A set of ``cbh_cross_upload``: N principals x M resources x A actions, decided tile by tile from the N + M rows."""
+
+    def __init__(self, table, h, n, m, a):
+        self.table, self.h, self.shape = table, h, (n, m, a)
+
+    def words(self, r_begin, r_end):
+        """64-bit words of one plane of the tile [r_begin, r_end)"""
+        return (self.shape[0] * (r_end - r_begin) + 63) // 64
+
+    def check(self, r_begin, r_end, flags=0, now_ns=0, want_flagged=False, into=None):
+        """``cbh_cross_check`` -> (allow, flagged or None): uint64[a][words] planes of ballots, action-major - bit q & 63 of
+        ``allow[k][q >> 6]`` = request ``q = (j' - r_begin) * n + i'`` of the tile is allowed action k; ``flagged``: its status is
+        not ST_OK.  ``into``: (allow, flagged) arrays to reuse, each uint64[a][>= words]."""
+        n, m, a = self.shape
+        w = self.words(r_begin, r_end) if r_end > r_begin else 0
+        if into is None:      # (at least a word per plane: an empty range is the library's to refuse, with its own text)
+            allow = np.zeros((a, max(w, 1)), dtype=np.uint64)
+            flagged = np.zeros((a, max(w, 1)), dtype=np.uint64) if want_flagged else None
+        else:
+            allow, flagged = into[0], (into[1] if want_flagged else None)
+        wpp = allow.shape[1] if allow.ndim == 2 else 0
+        if flagged is not None and flagged.shape != allow.shape:
+            raise ValueError("the allow and flagged planes must have one shape")
+        p = CParams(now_ns, flags, 0)
+        rc = load().cbh_cross_check(self.table.h, self.h, C.byref(p), r_begin, r_end, allow.ctypes.data if allow.size else None,
+                                    flagged.ctypes.data if flagged is not None and flagged.size else None, wpp)
+        if rc == 1:
+            raise DirectFormUnavailable(load().cbh_last_error().decode("utf-8", "replace"))
+        _check(rc)
+        return allow[:, :w], (flagged[:, :w] if flagged is not None else None)
+
+    def describe(self, flags=0):
+        """The kernel a ``check`` with these flags would launch (``cbh_cross_describe``), or "none: ..." ."""
+        p = CParams(0, flags, 0)
+        return load().cbh_cross_describe(self.table.h, self.h, C.byref(p)).decode()
+
+    def close(self):
+        if self.h:
+            load().cbh_cross_release(self.h)
             self.h = None
 
     def __del__(self):

@@ -115,6 +115,39 @@ def upload_halves(table, halves, n, m, act_ids, p_order, r_order, device_index=0
     return db
 
 
+def cross_direct_upload(table, flattener, columns, principals, resources, actions, aux_data=None,
+                        default_policy_version="default", default_scope="", sort=True, device_index=0):
+    """``cross_product_upload`` without the product (``capi.Table.cross_upload``): the device keeps the N + M halves and
+    ``capi.CrossSet.check`` decides tiles of resources straight from them - N * M is bounded by what the caller wants back, not by
+    device memory.  Returns the ``capi.CrossSet`` with ``shape``, ``p_order``, ``r_order`` (``allow_cube_planes`` accepts it), or
+    None where the set has no direct form: take ``cross_product_upload``, which gives the same answers."""
+    h, p_order, r_order, act_ids = cross_halves(flattener, principals, resources, actions, aux_data, default_policy_version, default_scope, sort)
+    return direct_upload_halves(table, h, len(principals), len(resources), act_ids, p_order, r_order, device_index)
+
+
+def direct_upload_halves(table, halves, n, m, act_ids, p_order, r_order, device_index=0):
+    """``cross_direct_upload`` for halves that are flattened already; an order of None is the identity."""
+    cs = table.cross_upload(halves, n, m, act_ids, p_order, r_order, device_index=device_index)
+    if cs is not None:
+        cs.p_order = np.arange(n) if p_order is None else np.asarray(p_order)
+        cs.r_order = np.arange(m) if r_order is None else np.asarray(r_order)
+    return cs
+
+
+def allow_cube_planes(cross_set, r_begin, r_end, planes):
+    """Planes of ``capi.CrossSet.check(r_begin, r_end)`` (``allow`` or ``flagged``: uint64[a][words]) -> bool[n][r_end - r_begin][a]
+    in the CALLER's orders: [i][j][k] = principals[i], the j-th of the tile's resources taken in the caller's resource order (the
+    tile holds resources ``r_order[r_begin:r_end]``), actions[k]."""
+    n, _, a = cross_set.shape
+    mt = r_end - r_begin
+    by = np.ascontiguousarray(planes, dtype="<u8").view(np.uint8).reshape(a, -1)
+    dev = np.unpackbits(by, axis=1, count=n * mt, bitorder="little").astype(bool).reshape(a, mt, n)   # [k][j'][i']
+    res = np.asarray(cross_set.r_order)[r_begin:r_end]
+    out = np.empty((n, mt, a), dtype=bool)
+    out[np.ix_(cross_set.p_order, np.argsort(np.argsort(res)))] = dev.transpose(2, 1, 0)
+    return out
+
+
 def allow_cube(batch, bits):
     """``capi.Table.download_allow_bits`` of the batch -> bool[n][m][a]: [i][j][k] = principals[i] may actions[k] on resources[j]."""
     n, m, a = batch.shape

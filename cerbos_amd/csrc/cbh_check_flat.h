@@ -443,8 +443,14 @@ __device__ __forceinline__ u64 load_u64g(const CBH_G u32* p) {   // 8-byte align
 // (cbh_check_flat_kernel_dr): the memo's registers cost the plain kernel a wave of occupancy and C2 2 % for nothing.
 // COMPACT: the request record, the 32-bit value planes and the tag planes of a resident batch (cbh_vm.h BatchDev.creq / cval / ctag) instead
 // of the wide arrays; the cache's tags are then in the packed form whatever the launch's flag says (the host sets it, and sizes the LDS).
-template <bool WITH_CALL, int MODE, bool EP = false, bool MEMO = false, bool COMPACT = false>
-__device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c) {
+// CROSS (implies COMPACT): the direct cross road (cerbos_hip.h cbh_cross_check).  The launch's batch is the compact form of the N + M
+// HALVES; a lane's request is a pair of their rows (CrossDev, cbh_check_wave.h): principal id, role count and role classes from the
+// principal's record, kind, version and scope from the resource's, the actions from the launch (the same for every lane), the
+// columns from either row by their side (cc_fill_cross).  The walk and the fold are the same; no result word is written - one
+// ballot per action (and one of "status is not OK", where wanted) is stored by the wave's first lane.
+template <bool WITH_CALL, int MODE, bool EP = false, bool MEMO = false, bool COMPACT = false, bool CROSS = false>
+__device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c, const CrossDev& x = CrossDev{}) {
+  static_assert(!CROSS || (COMPACT && !WITH_CALL && !EP && !MEMO), "the direct cross form: compact inputs, no evaluator call, no trail, no memo");
   constexpr bool STAGED = MODE == 1;
   constexpr u32 BTYPE = MODE == 2 ? (u32)CBH_B_RESSEG : (u32)CBH_B_RESOURCE;
   const TableDev& t = ka_regs.t;
@@ -461,12 +467,14 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c) {
 #else
 #define FLAT_DBG(x)
 #endif
-  const u32 rix = b.req_lo + blockIdx.x * CBH_FLAT_THREADS + threadIdx.x;
-  const bool valid = rix < b.req_hi;
-  const u32 req = valid ? rix : b.req_lo;
+  // (CROSS: the requests of the tile, from 0.  The bounds are read where they were read before the form existed: hoisting them
+  // into locals reordered two instructions of the trail kernels)
+  const u32 rix = (CROSS ? 0u : b.req_lo) + blockIdx.x * CBH_FLAT_THREADS + threadIdx.x;
+  const bool valid = rix < (CROSS ? x.n_tile : b.req_hi);
+  const u32 req = valid ? rix : (CROSS ? 0u : b.req_lo);
   const u32 NR = b.n_requests;
-  const u32 w0r = b.req_lo + blockIdx.x * CBH_FLAT_THREADS + wave * CBH_BLOCK;
-  const u32 w0 = w0r < b.req_hi ? w0r : b.req_lo;   // the wave's first request (uniform): the columns' planes are addressed from it
+  const u32 w0r = (CROSS ? 0u : b.req_lo) + blockIdx.x * CBH_FLAT_THREADS + wave * CBH_BLOCK;
+  const u32 w0 = w0r < (CROSS ? x.n_tile : b.req_hi) ? w0r : (CROSS ? 0u : b.req_lo);   // the wave's first request (uniform): the columns' planes are addressed from it
   const u32 wd = valid ? c.tid : 0u;                // ... and this lane's distance from it
   const u32 kmax = t.K ? t.K - 1u : 0u;
   u32 pid, kind, r_scope, r_ver, role_off = 0, act_off, role_cnt, act_cnt;
@@ -474,7 +482,23 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c) {
   u32x4u sp{0, 0, 0, 0};
   u32 cls_a0 = 0, cls_r0 = 0;
   bool spec = false; u32 spec_ix = 0;
-  if constexpr (COMPACT) {
+  u32 x_prow = 0, x_rrow = 0;   // CROSS: the lane's two rows of the halves
+  if constexpr (CROSS) {
+    // ---- the pair (cbh_cross.h: resource-major, q = j' * N + i').  A lane beyond the tile's end shadows q = 0 with no action and no role.
+    const u32 jp = req / x.n, ip = req - jp * x.n;
+    x_prow = x.p_order ? x.p_order[ip] : ip;
+    x_rrow = x.n + (x.r_order ? x.r_order[x.r_begin + jp] : x.r_begin + jp);
+    const u32x4u prec = load_u32x4(b.creq + 4u * (size_t)x_prow), rrec = load_u32x4(b.creq + 4u * (size_t)x_rrow);
+    pid = prec.x; kind = rrec.y & 0xFFFFu; r_ver = rrec.y >> 16;
+    r_scope = (rrec.z & 0xFFFFu) | (rrec.w & CBH_SCOPE_EXACT);
+    role_cnt = valid ? (prec.z >> 16) & 7u : 0u; act_cnt = valid ? (x.act_word >> 20) & 7u : 0u;   // both <= 4
+#pragma unroll
+    for (u32 k = 0; k < 4; ++k) ac[k] = valid ? (x.act_word >> (5u * k)) & 31u : 31u;
+    rc[0] = (prec.w >> 20) & 31u; rc[1] = (prec.w >> 25) & 31u; rc[2] = (prec.z >> 22) & 31u; rc[3] = prec.z >> 27;
+#pragma unroll
+    for (u32 k = 0; k < 4; ++k) rc[k] = valid ? rc[k] : 31u;
+    act_off = 0;
+  } else if constexpr (COMPACT) {
     // ---- the compact form (cbh_vm.h BatchDev.creq): ONE 16-byte load brings everything the walk takes from the request words, the
     // role ids and the action ids - the classes were looked up when the batch was uploaded.  First trip: the record; second:
     // the columns' and the tags' copies (cc_fill_compact) and the chain's first scope.  No class table is read, none is staged in LDS, and the
@@ -557,7 +581,7 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c) {
   CBH_L u32* ep_lds = (CBH_L u32*)(cls_lds + (cls_in_lds ? ((2u * t.K + 15u) & ~15u) : 0u) + (MODE == 2 ? CBH_FLAT_WAVES * CBH_SEG_LDS_BYTES : 0u)) + wave * max_depth * 2u * CBH_BLOCK;
   const bool want_ep = EP && (flags & CBH_F_WANT_EFFECTIVE_POLICIES) != 0 && o.eff_pol != nullptr;
   if (EP) { for (u32 d = 0; d < 2u * max_depth; ++d) ep_lds[d * CBH_BLOCK + c.tid] = 0; }
-  if constexpr (COMPACT) cc_fill_compact(c, b, NR, w0, wd); else cc_fill(c, b, NR, w0, wd, cct);   // (behind every LDS store of this prologue)
+  if constexpr (CROSS) cc_fill_cross(c, b, NR, x_prow, x_rrow, x.side); else if constexpr (COMPACT) cc_fill_compact(c, b, NR, w0, wd); else cc_fill(c, b, NR, w0, wd, cct);   // (behind every LDS store of this prologue)
   // ... and the chain's first scope (ruletable.go:848-882; per lane, reads the scope tables): its load goes out with the second trip
   const bool lenient = (flags & CBH_F_LENIENT_SCOPE_SEARCH) != 0;
   const u32 first = chain_first(t, r_scope, FLAG_RES, lenient);
@@ -604,8 +628,10 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c) {
   auto leafish = [&](u32 ref, u32 how, const LeafRec& lr, bool active) -> u32 {
     u32 lv = 4u;
     FLAT_DBG(const u64 e0 = __builtin_readcyclecounter(); ++dbg_evals;)
-    if (how == 1u) lv = flat_leaf<WITH_CALL, COMPACT>(c, lr, req, pid);
-    else if (how == 2u) lv = flat_tree<WITH_CALL, COMPACT>(c, lr, req, pid);
+    // (CROSS: the membership leaves too - their lists lie in the heap the halves share.  A direct launch also serves the flat tables
+    // that are not closed over the classified leaves; what the inline code leaves open there comes back UNSUPPORTED - flagged - below)
+    if (how == 1u) lv = flat_leaf<WITH_CALL || CROSS, COMPACT>(c, lr, req, pid);
+    else if (how == 2u) lv = flat_tree<WITH_CALL || CROSS, COMPACT>(c, lr, req, pid);
     FLAT_DBG(cyc_eval += (__builtin_readcyclecounter() - e0) * (u64)(wave_ballot(lv != 77u) != 0);)
     const bool slow = active && lv == 4u;
     if (WITH_CALL) {
@@ -1098,6 +1124,22 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c) {
     if (dr_unsup) st4 = 0x02020202u;
   }
 
+  if constexpr (CROSS) {
+    // ---- the planes.  One ballot per action, every lane voting (a lane beyond the tile's end: no); the wave's first lane stores the
+    // word to [action][the wave's number in the tile] - a plane word is exactly one ballot, whatever the action count.
+    const u32 xa = (x.act_word >> 20) & 7u, word = w0r >> 6;   // uniform
+#pragma unroll
+    for (u32 k = 0; k < 4; ++k) {
+      const bool in = valid && k < act_cnt;
+      const u64 ma = wave_ballot(in && alw[k]);
+      const u64 mf = wave_ballot(in && ((st4 >> (8u * k)) & 0xFFu) != (u32)CBH_ST_OK);
+      if (c.tid == 0 && k < xa && w0r < x.n_tile) {
+        x.allow[(size_t)k * x.words + word] = ma;
+        if (x.flagged) x.flagged[(size_t)k * x.words + word] = mf;
+      }
+    }
+    return;
+  }
   // (compact form: only the stores need the offset - a load up here, inside a uniform branch, would be waited for in the prologue)
   if constexpr (COMPACT) { if (!(b.compact_info & CBH_CI_ACT4)) act_off = b.req_u32[(size_t)CBH_RQ_ACT_OFF * NR + req]; }
   const bool packed = valid && act_cnt == 4 && (act_off & 3u) == 0;
@@ -1307,6 +1349,40 @@ static inline cbh_check_kernel_fn cbh_flat_compact_variant(cbh_check_kernel_fn f
 // ... whose column cache always keeps its tags in the packed form (cbh_vm.h CBH_CC_DWORDS): the launch is sized for it
 static inline bool cbh_is_flat_compact_kernel(cbh_check_kernel_fn fn) {
   return fn == cbh_check_flat_kernel_c || fn == cbh_check_flat_kernel_staged_c || fn == cbh_check_flat_kernel_masks_c;
+}
+// The direct cross road's instantiations (flat_body CROSS; cerbos_hip.h cbh_cross_check): MODE 0, 1, 2 without the evaluator call, the
+// cross arguments a by-value parameter of their own.  Same attributes as their compact siblings.
+__global__ CBH_FLAT_ATTRS(7) void cbh_check_flat_kernel_x(const KernelArgs a, const KernelArgs* __restrict__ ka, const CrossDev x) {
+  CBH_FLAT_CTX_C(a, ka);
+  flat_body<false, 0, false, false, true, true>(a, c, x);
+}
+__global__ CBH_FLAT_ATTRS(5) void cbh_check_flat_kernel_staged_x(const KernelArgs a, const KernelArgs* __restrict__ ka, const CrossDev x) {
+  CBH_FLAT_CTX_C(a, ka);
+  flat_body<false, 1, false, false, true, true>(a, c, x);
+}
+__global__ CBH_FLAT_ATTRS(4) void cbh_check_flat_kernel_masks_x(const KernelArgs a, const KernelArgs* __restrict__ ka, const CrossDev x) {
+  CBH_FLAT_CTX_C(a, ka);
+  flat_body<false, 2, false, false, true, true>(a, c, x);
+}
+typedef void (*cbh_cross_kernel_fn)(const KernelArgs, const KernelArgs*, const CrossDev);
+// The direct instantiation of the kernel a plan picks, by its MODE, or null where it has none (the derived-role variant, the trail's,
+// the mask walk with the call).  A table that is not closed over the classified leaves is planned an `_any` kernel even for a batch of
+// plain tags (the host refuses the other batches).  For MODE 0 and 1 its direct sibling is the same instantiation: there every
+// condition goes through `leafish`, which in a CROSS instantiation decides the membership leaves inline and marks what only the
+// evaluator call could decide UNSUPPORTED, which the caller sees in the `flagged` planes.  NOT for MODE 2: the mask walk evaluates
+// leaves in blocks (leaf_block_codes) that know classes 1-4 and 6 only - a membership leaf there would make every candidate of its
+// segment UNSUPPORTED - so cbh_check_flat_kernel_any_masks has no direct form and the set takes the materialised road.
+static inline int cbh_flat_cross_mode(cbh_check_kernel_fn fn) {
+  return (fn == cbh_check_flat_kernel || fn == cbh_check_flat_kernel_any) ? 0 : (fn == cbh_check_flat_kernel_staged || fn == cbh_check_flat_kernel_any_staged) ? 1
+       : fn == cbh_check_flat_kernel_masks ? 2 : -1;
+}
+static inline cbh_cross_kernel_fn cbh_flat_cross_variant(cbh_check_kernel_fn fn) {
+  const int m = cbh_flat_cross_mode(fn);
+  return m == 0 ? cbh_check_flat_kernel_x : m == 1 ? cbh_check_flat_kernel_staged_x : m == 2 ? cbh_check_flat_kernel_masks_x : nullptr;
+}
+static inline const char* cbh_flat_cross_name(cbh_check_kernel_fn fn) {
+  const int m = cbh_flat_cross_mode(fn);
+  return m == 0 ? "cbh_check_flat_kernel_x" : m == 1 ? "cbh_check_flat_kernel_staged_x" : m == 2 ? "cbh_check_flat_kernel_masks_x" : "";
 }
 #define CBH_FLAT_STAGE_MIN 32u
 // the mask walk decides a table that has segments and long buckets (CBH_FLAT_MASKS=0: never, =1: whatever the buckets' length - tests, A/B)

@@ -518,6 +518,64 @@ __device__ __forceinline__ void cc_fill_compact(const Ctx& c, const BatchDev& b,
   }
 }
 
+// What the direct cross kernels (cbh_check_flat.h flat_body CROSS; cerbos_hip.h cbh_cross_check) take beside KernelArgs, as a
+// kernel parameter of their own - KernelArgs, BatchDev and OutDev keep their layout.  The batch of the launch is the HALVES batch
+// in its compact form (N principals' rows, then M resources'); request q of the tile pairs principal p_order[q % n] with resource
+// r_order[r_begin + q / n].
+struct CrossDev {
+  const CBH_G u32* p_order; const CBH_G u32* r_order;   // [n], [m], or null = identity
+  CBH_G u64* allow; CBH_G u64* flagged;                 // [actions][words] ballots, action-major; flagged: null = not wanted
+  u32 n, r_begin, n_tile, words;                        // principals; first resource of the tile; its requests n * (r_end - r_begin); (n_tile + 63) / 64
+  u32 side;                                             // bit k = cached column k travels with the resource (CrossArgs.col_side)
+  u32 act_word;                                         // action classes 0..3 (5 bits each, as in word 3 of a compact record) | action count << 20
+};
+// cc_fill_compact for a lane whose request is a PAIR of rows of the halves' compact form: column k's copies read at the resource's
+// row where bit k of `side` (wave-uniform) is set, at the principal's otherwise - lds_dma_dword takes a per-lane address.  The tags:
+// a group of four columns of ONE side is one copy of the lane's dword of that row's `ctag` plane, as in cc_fill_compact; a group
+// that MIXES sides has its bytes in two rows - both dwords are loaded, merged under the group's side mask and stored, before any
+// asynchronous copy goes out (an LDS access behind the copies waits for all of them).
+__device__ __forceinline__ void cc_fill_cross(const Ctx& c, const BatchDev& b, u32 NR, u32 prow, u32 rrow, u32 side) {
+  const u32 narrow = b.compact_info & CBH_CI_NARROW_MASK;   // uniform
+  CBH_L u32* tags = c.cc + 2u * c.n_cached * CBH_BLOCK;
+  const u32 have = c.n_cached >= 32u ? 0xFFFFFFFFu : (1u << c.n_cached) - 1u;   // the columns that exist
+  u32 mixed = 0, tp[CBH_CACHE_COLS / 4], tr[CBH_CACHE_COLS / 4];
+#pragma unroll
+  for (u32 g = 0; g < CBH_CACHE_COLS / 4; ++g) {
+    const u32 hg = (have >> (4u * g)) & 0xFu, sg = (side >> (4u * g)) & hg;
+    tp[g] = 0; tr[g] = 0;
+    if (sg != 0 && sg != hg) {   // uniform
+      mixed |= 1u << g;
+      tp[g] = b.ctag[(size_t)g * NR + prow]; tr[g] = b.ctag[(size_t)g * NR + rrow];
+    }
+  }
+#pragma unroll
+  for (u32 g = 0; g < CBH_CACHE_COLS / 4; ++g) {
+    if ((mixed >> g) & 1u) {
+      const u32 sg = side >> (4u * g);
+      const u32 m = ((sg & 1u) ? 0xFFu : 0u) | ((sg & 2u) ? 0xFF00u : 0u) | ((sg & 4u) ? 0xFF0000u : 0u) | ((sg & 8u) ? 0xFF000000u : 0u);
+      tags[g * CBH_BLOCK + c.tid] = (tr[g] & m) | (tp[g] & ~m);
+    }
+  }
+  for (u32 k = 0; k < c.n_cached; ++k) if ((narrow >> k) & 1u) c.cc[(c.n_cached + k) * CBH_BLOCK + c.tid] = 0u;
+  for (u32 g = 0; 4u * g < c.n_cached; ++g) {
+    if ((mixed >> g) & 1u) continue;
+    const u32 row = ((side & have) >> (4u * g)) & 0xFu ? rrow : prow;
+    lds_dma_dword(b.ctag + ((size_t)g * NR + row), tags + g * CBH_BLOCK, c.tid);
+  }
+  u32 plane = 0;   // narrow planes in front of column k (uniform)
+  for (u32 k = 0; k < c.n_cached; ++k) {
+    const u32 row = ((side >> k) & 1u) ? rrow : prow;
+    if ((narrow >> k) & 1u) {
+      lds_dma_dword(b.cval + ((size_t)plane * NR + row), c.cc + k * CBH_BLOCK, c.tid);
+      ++plane;
+    } else {
+      const CBH_G u32* vb = (const CBH_G u32*)(b.col_val + ((size_t)k * NR + row));
+      lds_dma_dword(vb, c.cc + k * CBH_BLOCK, c.tid);
+      lds_dma_dword(vb + 1, c.cc + (c.n_cached + k) * CBH_BLOCK, c.tid);
+    }
+  }
+}
+
 struct CbhPassPrincipal { static constexpr bool value = false; };   // tags of the two instantiations of the
 struct CbhPassResource { static constexpr bool value = true; };     // policy pass (check_body below)
 

@@ -1,6 +1,8 @@
 // Cross-product batches built on the device (cerbos_hip.h cbh_batch_upload_cross) and the allow bitmap of a resident batch
 // (cbh_result_download_allow_bits).  Three small kernels, none of them on the decision path: the product they build is an ordinary
-// resident batch the decision kernels read unchanged.
+// resident batch the decision kernels read unchanged.  And the one-lane kernel of the DIRECT road (cbh_cross_upload), which
+// materialises no product: its decision kernels are the flat kernels' CROSS instantiations (cbh_check_flat.h), which read the
+// halves' compact form in place and write ballots.
 //
 // The product's layout: N principals x M resources, resource-major.  Device request q = j' * N + i' pairs the
 // j'-th resource with the i'-th principal of the caller's orders; the halves batch holds the N principals in its first N
@@ -78,4 +80,19 @@ __global__ __launch_bounds__(256) void cbh_allow_bits_kernel(AllowBitsArgs a) {
   if (k < a.n_tuples) eff = a.packed ? cbh_pk_effect(a.packed[k]) : (u32)a.effect[k];
   const u64 mask = wave_ballot(eff == CBH_EFFECT_ALLOW);
   if ((threadIdx.x & 63u) == 0u && k < a.n_tuples) a.bits[k >> 6] = mask;
+}
+
+// The direct road's action word (CrossDev.act_word): the classes of the A <= 4 actions every request asks for, by the expressions of
+// cbh_compact_pack_kernel (clamps included), five bits each as in word 3 of a compact record, and A << 20.  One lane, once per upload.
+struct CrossActWordArgs { const CBH_G u32* action_ids; const CBH_G u8* action_class; CBH_G u32* out; u32 a, K; };
+__global__ __launch_bounds__(64) void cbh_cross_act_word_kernel(CrossActWordArgs x) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  const u32 kmax = x.K ? x.K - 1u : 0u;
+  u32 w = x.a << 20;
+  for (u32 k = 0; k < 4; ++k) {
+    const u32 aid = x.action_ids[k < x.a ? k : 0u];
+    const u32 ca = x.K ? x.action_class[aid < x.K ? aid : kmax] : 31u;
+    w |= ((k < x.a && aid < x.K && ca < 31u) ? ca : 31u) << (5u * k);
+  }
+  x.out[0] = w;
 }

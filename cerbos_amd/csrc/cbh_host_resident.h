@@ -199,24 +199,24 @@ extern "C" int cbh_batch_upload(cbh_table* t, const cbh_batch* in, cbh_device_ba
 // ---- cross-product batches: N + M halves up, the N x M product built in device memory (cbh_cross.h) ------------------------
 // The batch's shape comes from the halves, looking only at the rows the product uses, so that the product gets the plan a
 // host-built batch of the same requests gets (validate_batch's answers for that batch, without the batch).
-static int cross_upload(cbh_table* t, uint32_t device_index, const cbh_batch* h, const cbh_cross* x, cbh_device_batch** out) {
-  if (!t || !h || !x || !out) return fail("null argument");
-  *out = nullptr;
+// (`bounded`: the product is materialised, so N * M and N * M * A must stay below 2^32 - the direct road, cbh_cross_upload, has no such bound)
+struct CrossShape { std::vector<u8> side; u32 maxr = 0, wide_lo = 0, wide_hi = 0; bool plain = true; };
+static int cross_validate(cbh_table* t, uint32_t device_index, const cbh_batch* h, const cbh_cross* x, bool bounded, CrossShape& cs) {
   if (device_index >= t->reps.size()) return fail("device index out of range");
   const u64 N = x->n_principals, M = x->n_resources, A = x->n_actions;
   if (!N || !M || !A) return fail("cbh_cross: n_principals, n_resources and n_actions must be at least 1");
   if (A > CBH_MAX_ACTIONS_PER_REQUEST) return fail("cbh_cross: more than CBH_MAX_ACTIONS_PER_REQUEST actions");
   if (!x->action_ids) return fail("null argument");
   if ((u64)h->n_requests != N + M) return fail("cbh_cross: the halves batch must hold n_principals + n_resources requests");
-  if (N * M >= (1ull << 32) || N * M * A >= (1ull << 32)) return fail("cbh_cross: the product has 2^32 requests or tuples, or more: split the resources");
+  if (bounded && (N * M >= (1ull << 32) || N * M * A >= (1ull << 32))) return fail("cbh_cross: the product has 2^32 requests or tuples, or more: split the resources");
   const u32 ncol = h->n_columns;
   if (ncol != t->meta[CBH_M_NCOLUMNS]) return fail("cbh_batch.n_columns does not match the table's column schema");
   if (t->wire.cols.size() < ncol) return fail("the image names no column paths (CBH_SEC_COLUMN_PATHS): which half a column comes from is unknown");
   if (!h->req_u32 || (h->n_roles && !h->roles) || (ncol && (!h->col_tag || !h->col_val)) || (h->heap_len && (!h->heap_tag || !h->heap_val)) ||
       (h->n_strings && (!h->str_off || !h->str_flags)) || (h->str_bytes_len && !h->str_bytes)) return fail("cbh_batch: a required array is NULL");
   if (h->n_strings && h->str_off[h->n_strings] > h->str_bytes_len) return fail("cbh_batch: string offsets exceed str_bytes_len");
-  const size_t NH = (size_t)(N + M), NM = (size_t)(N * M), NT = (size_t)(N * M * A);
-  std::vector<u8> side, seen;
+  const size_t NH = (size_t)(N + M), NM = (size_t)(N * M);
+  std::vector<u8>& side = cs.side; std::vector<u8> seen;
   try { side.assign(ncol ? ncol : 1, 0); seen.assign(std::max(N, M), 0); } catch (...) { return fail("out of memory"); }
   for (u32 c = 0; c < ncol; ++c) side[c] = t->wire.cols[c].root == 1 ? 1 : 0;
   for (int which = 0; which < 2; ++which) {   // the orders are permutations
@@ -253,6 +253,19 @@ static int cross_upload(cbh_table* t, uint32_t device_index, const cbh_batch* h,
       hit = side[c] ? BatchShape::has_int_or_container_tag(h->col_tag + (size_t)c * NH + N, M) : BatchShape::has_int_or_container_tag(h->col_tag + (size_t)c * NH, N);
     plain = !flat_any_forced() && !hit;
   }
+  cs.maxr = maxr; cs.wide_lo = wide_lo; cs.wide_hi = wide_hi; cs.plain = plain;
+  return 0;
+}
+static int cross_upload(cbh_table* t, uint32_t device_index, const cbh_batch* h, const cbh_cross* x, cbh_device_batch** out) {
+  if (!t || !h || !x || !out) return fail("null argument");
+  *out = nullptr;
+  CrossShape cs;
+  if (cross_validate(t, device_index, h, x, true, cs) != 0) return -1;
+  const u64 N = x->n_principals, M = x->n_resources, A = x->n_actions;
+  const u32 ncol = h->n_columns;
+  const size_t NH = (size_t)(N + M), NM = (size_t)(N * M), NT = (size_t)(N * M * A);
+  const std::vector<u8>& side = cs.side;
+  const u32 maxr = cs.maxr, wide_lo = cs.wide_lo, wide_hi = cs.wide_hi; const bool plain = cs.plain;
   Replica* rep = t->reps[device_index];
   HIPCHK(hipSetDevice(rep->device));
   cbh_device_batch* b = batch_new(t, rep, false);
@@ -617,6 +630,143 @@ extern "C" int cbh_result_download_allow_bits(cbh_table* t, cbh_device_batch* b,
   HIPCHK(hipStreamSynchronize(s));
   collect_times(rep);
   return 0;
+}
+
+
+// ---- the direct cross road: N x M decided straight from the N + M halves (cerbos_hip.h cbh_cross_upload / cbh_cross_check) ----
+// The set is the HALVES as a resident batch in its compact form (batch_upload + batch_compact, unchanged: the device holds N + M
+// rows), the two orders, the columns' sides as a mask and the actions' classes as one word.  A check launches the `_x` sibling of
+// the kernel plan_for picks for (A actions, the principals' roles, plain tags) with the compact launch's LDS, over the tile's
+// N * (r_end - r_begin) pairs; what comes back is one ballot word per 64 pairs and action.  The planes' device words belong to the
+// set's batch (the replica's pool) and serve every tile that fits them.
+struct cbh_cross_set {
+  cbh_device_batch* b = nullptr;
+  u32 n = 0, m = 0, a = 0, maxr = 0; bool plain = true;
+  const u32* p_order = nullptr; const u32* r_order = nullptr;   // device, or null = identity
+  u32 side = 0, act_word = 0;
+  u64* planes = nullptr; size_t plane_cap = 0;   // [allow | flagged][a][words]
+};
+static cbh_cross_kernel_fn cross_kernel_for(const cbh_cross_set* cs, u32 eval_flags, CbhPlan& pl) {
+  pl = plan_for(cs->b->rep->dev, cs->a, cs->maxr, cs->plain, eval_flags & ~(u32)CBH_FI_MASK);
+  if (pl.kind != 1 || (eval_flags & CBH_F_DEBUG_CYCLES)) return nullptr;
+  return cbh_flat_cross_variant(pl.kernel);
+}
+static int cross_set_upload(cbh_table* t, uint32_t device_index, const cbh_batch* h, const cbh_cross* x, cbh_cross_set** out) {
+  if (out) *out = nullptr;
+  if (!t || !h || !x || !out) return fail("null argument");
+  CrossShape shape;
+  if (cross_validate(t, device_index, h, x, false, shape) != 0) return -1;
+  Replica* rep = t->reps[device_index];
+  const u32 N = x->n_principals, M = x->n_resources, A = x->n_actions;
+  // no direct form: the caller takes cbh_batch_upload_cross, which gives the same answers
+  if (!(rep->dev.flags & CBH_MF_FLAT)) { g_err = "cbh_cross_upload: no direct form - the table is not flat"; return 1; }
+  if (rep->dev.n_dr) { g_err = "cbh_cross_upload: no direct form - the table has derived roles"; return 1; }
+  if (A > 4) { g_err = "cbh_cross_upload: no direct form - more than four actions"; return 1; }
+  if (shape.maxr > 4) { g_err = "cbh_cross_upload: no direct form - a principal has more than four roles"; return 1; }
+  if (!shape.plain) { g_err = "cbh_cross_upload: no direct form - an attribute value needs the evaluator (int / uint / list / map in a sensitive column)"; return 1; }
+  if (!compact_inputs_on()) { g_err = "cbh_cross_upload: no direct form - compact inputs are switched off"; return 1; }
+  {   // the kernel the product would be planned (mask walk of a table that is not closed over the classified leaves: cbh_flat_cross_mode)
+    const CbhPlan pl = plan_for(rep->dev, A, shape.maxr, shape.plain, 0);
+    if (pl.kind != 1 || !cbh_flat_cross_variant(pl.kernel)) { g_err = "cbh_cross_upload: no direct form - the kernel planned for this table has no direct instantiation"; return 1; }
+  }
+  cbh_cross_set* cs = new (std::nothrow) cbh_cross_set();
+  if (!cs) return fail("out of memory");
+  cs->n = N; cs->m = M; cs->a = A; cs->maxr = shape.maxr; cs->plain = shape.plain;
+  for (u32 c = 0; c < h->n_columns && c < CBH_CACHE_COLS; ++c) if (shape.side[c]) cs->side |= 1u << c;
+  // the halves: an ordinary resident batch of N + M requests (validated as one: the scan and the pack read every row's role and
+  // action slices) with its compact form
+  if (batch_upload(t, device_index, h, &cs->b, true) != 0) { delete cs; return -1; }
+  cbh_device_batch* b = cs->b;
+  auto drop = [&](int rc) { cbh_batch_release(b); delete cs; return rc; };
+  b->max_actions = A; b->max_roles = shape.maxr; b->plain_tags = shape.plain;   // (the PRODUCT's shape: what a plan is made for)
+  if (!b->compact) { g_err = "cbh_cross_upload: no direct form - a field of the halves does not fit the compact record (CBH_CI_MISFIT)"; return drop(1); }
+  hipStream_t s = b->stream;
+  const u32* d_act = nullptr; u32* d_word = nullptr;
+  int rc = 0;
+  if (x->p_order) rc |= up(b, cs->p_order, x->p_order, (size_t)N, s);
+  if (x->r_order) rc |= up(b, cs->r_order, x->r_order, (size_t)M, s);
+  rc |= up(b, d_act, x->action_ids, (size_t)A, s);
+  rc |= dalloc(b, d_word, 1);
+  if (rc != 0) return drop(-1);
+  CrossActWordArgs wa{}; wa.action_ids = d_act; wa.action_class = rep->dev.action_class; wa.out = d_word; wa.a = A; wa.K = rep->dev.K;
+  hipLaunchKernelGGL(cbh_cross_act_word_kernel, dim3(1), dim3(64), 0, s, wa);
+  if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&cs->act_word, d_word, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+    (void)hipGetLastError(); fail("cbh_cross_upload: upload failed"); return drop(-1);
+  }
+  *out = cs;
+  return 0;
+}
+extern "C" int cbh_cross_upload(cbh_table* t, uint32_t device_index, const cbh_batch* halves, const cbh_cross* x, cbh_cross_set** out) {
+  try { return cross_set_upload(t, device_index, halves, x, out); } catch (...) { return fail("out of memory"); }
+}
+static int cross_set_check(cbh_table* t, cbh_cross_set* cs, const cbh_params* p, uint32_t r_begin, uint32_t r_end, uint64_t* allow, uint64_t* flagged, size_t words_per_plane) {
+  if (!t || !cs || !p || !allow) return fail("null argument");
+  cbh_device_batch* b = cs->b;
+  if (b->table != t) return fail("the set was uploaded for a different table");
+  if (r_begin >= r_end || r_end > cs->m) return fail("cbh_cross_check: [r_begin, r_end) must be a non-empty range of the set's resources");
+  const u64 nt = (u64)cs->n * (r_end - r_begin);
+  if (nt >= (1ull << 32)) return fail("cbh_cross_check: the tile has 2^32 requests or more: take fewer resources");
+  const size_t W = (size_t)((nt + 63) / 64);
+  if (words_per_plane < W) return fail("cbh_cross_check: words_per_plane is less than (n_principals * (r_end - r_begin) + 63) / 64");
+  CbhPlan pl;
+  const cbh_cross_kernel_fn fn = cross_kernel_for(cs, p->flags, pl);
+  if (!fn) { g_err = "cbh_cross_check: these flags choose a plan without a direct form"; return 1; }
+  Replica* rep = b->rep;
+  std::lock_guard<std::mutex> lk(rep->mu);
+  HIPCHK(hipSetDevice(rep->device));
+  hipStream_t s = b->stream;
+  const size_t per = (size_t)cs->a * W, need = per * (flagged ? 2 : 1);
+  if (need > cs->plane_cap) {
+    // a larger tile than any before: a new block, and the old one back to the replica's pool (every check ends with a wait for its
+    // copies, so nothing of the stream still reads it)
+    u64* np = nullptr;
+    if (dalloc(b, np, need) != 0) return -1;
+    if (cs->planes) {
+      for (size_t i = 0; i < b->allocs.size(); ++i) if (b->allocs[i].first == (void*)cs->planes) {
+        { std::lock_guard<std::mutex> pl(rep->pool_mu); rep->pool_free.push_back(b->allocs[i]); }
+        b->allocs[i] = b->allocs.back(); b->allocs.pop_back();
+        break;
+      }
+    }
+    cs->planes = np; cs->plane_cap = need;
+  }
+  KernelArgs ka;
+  std::memset(&ka, 0, sizeof(ka));
+  ka.t = rep->dev; ka.b = b->dev; ka.now_ns = p->now_ns;
+  ka.flags = (p->flags & ~(u32)CBH_FI_MASK) | CBH_FI_COMPACT | CBH_FI_PACKED_TAGS;   // (a compact launch: the cache's tags in the packed form)
+  CrossDev x{};
+  x.p_order = cs->p_order; x.r_order = cs->r_order; x.allow = cs->planes; x.flagged = flagged ? cs->planes + per : nullptr;
+  x.n = cs->n; x.r_begin = r_begin; x.n_tile = (u32)nt; x.words = (u32)W; x.side = cs->side; x.act_word = cs->act_word;
+  const TableDev& dev = rep->dev;
+  const size_t lds = cbh_plan_lds(pl, dev.flags, dev.max_depth, dev.n_scopes, dev.K, ka.b.n_columns, dev.inline_cols, dev.n_dr, false, CBH_W2_NA, true) + lds_pad();
+  hipLaunchKernelGGL(fn, dim3((u32)((nt + pl.threads - 1) / pl.threads)), dim3(pl.threads), lds, s, ka, (const KernelArgs*)nullptr, x);   // (the arguments in memory are the evaluator call's: no _x kernel has one)
+  HIPCHK(hipGetLastError());
+  for (int which = 0; which < (flagged ? 2 : 1); ++which) {
+    uint64_t* dst = which ? flagged : allow; const u64* src = cs->planes + (size_t)which * per;
+    if (words_per_plane == W) HIPCHK(hipMemcpyAsync(dst, src, per * 8, hipMemcpyDeviceToHost, s));
+    else for (u32 k = 0; k < cs->a; ++k) HIPCHK(hipMemcpyAsync(dst + (size_t)k * words_per_plane, src + (size_t)k * W, W * 8, hipMemcpyDeviceToHost, s));
+  }
+  HIPCHK(hipStreamSynchronize(s));
+  return 0;
+}
+extern "C" int cbh_cross_check(cbh_table* t, cbh_cross_set* cs, const cbh_params* p, uint32_t r_begin, uint32_t r_end, uint64_t* allow, uint64_t* flagged, size_t words_per_plane) {
+  try { return cross_set_check(t, cs, p, r_begin, r_end, allow, flagged, words_per_plane); } catch (...) { return fail("out of memory"); }
+}
+extern "C" const char* cbh_cross_describe(cbh_table* t, cbh_cross_set* cs, const cbh_params* p) {
+  static thread_local std::string s;
+  if (!t || !cs || !p) return "";
+  try {
+    CbhPlan pl;
+    if (cs->b->table != t) s = "none: the set was uploaded for a different table";
+    else if (!cross_kernel_for(cs, p->flags, pl)) s = "none: these flags choose a plan without a direct form";
+    else { char m[96]; snprintf(m, sizeof m, "[direct cross, %u + %u rows, narrow columns 0x%x]", cs->n, cs->m, cs->b->dev.compact_info & CBH_CI_NARROW_MASK); s = std::string(cbh_flat_cross_name(pl.kernel)) + m; }
+  } catch (...) { return ""; }
+  return s.c_str();
+}
+extern "C" void cbh_cross_release(cbh_cross_set* cs) {
+  if (!cs) return;
+  cbh_batch_release(cs->b);
+  delete cs;
 }
 
 

@@ -283,7 +283,7 @@ int cbh_kernel_time_ms(cbh_table* t, float* check_kernel_ms, float* resolve_kern
  * range, a device allocation that fails.
  * Not here: one product sharded over several devices (split the resources and call once per device);
  * cbh_check_batch_trail / cbh_trace_batch on a product (flatten the few inputs marked CBH_ST_CEL_ERROR / CBH_ST_WANTS_TRACE
- * explicitly and trace those); deciding straight from the halves without materialising the product. */
+ * explicitly and trace those).  Deciding straight from the halves without materialising the product: cbh_cross_upload, below. */
 #define CBH_HAS_CROSS 1
 typedef struct cbh_cross {
   uint32_t n_principals, n_resources, n_actions; /* N, M, A */
@@ -296,6 +296,47 @@ int cbh_batch_upload_cross(cbh_table* t, uint32_t device_index, const cbh_batch*
  * the batch's device order, unused bits of the last word 0; n_words >= (n_tuples + 63) / 64 or the call fails and writes
  * nothing.  Any resident batch; a later cbh_result_download still gives the full results. */
 int cbh_result_download_allow_bits(cbh_table* t, cbh_device_batch* b, uint64_t* bits, size_t n_words);
+
+/* ---- The direct road: N x M decided straight from the halves, one bit per decision, tile by tile -----------------
+ * cbh_batch_upload_cross materialises the product: about 134 B of device memory per request, and N * M below 2^32.  The direct
+ * road materialises nothing: the device holds the N + M rows of `halves` (in the flat kernels' compact form), and
+ * cbh_cross_check decides the resources [r_begin, r_end) of the device order against all N principals - request
+ * q = (j' - r_begin) * N + i' of the tile pairs resource j' with principal i', as in the product - reading the two rows in place.
+ * N * M is not bounded; a tile is: N * (r_end - r_begin) < 2^32.  The caller chooses the tiles by what it wants back.
+ *
+ * What comes back: PLANES of ballots, action-major.  With W = (N * (r_end - r_begin) + 63) / 64, bit (q & 63) of
+ * allow[k * words_per_plane + (q >> 6)] = request q of the tile is allowed action k (k < A; unused bits of a plane's last word
+ * are 0; the words between W and words_per_plane are not written).  This is NOT the tuple order of
+ * cbh_result_download_allow_bits (bit q * A + k): a plane word is exactly one wave's ballot, whatever A is.  `flagged` (or NULL):
+ * planes of the same layout, bit set = the tuple's status is not CBH_ST_OK (a CEL error, CBH_ST_WANTS_TRACE) - the tuples to take
+ * to another road for their full result; the library never hides a status behind a bit.
+ *
+ * cbh_cross_upload: `halves` and `x` as for cbh_batch_upload_cross; in addition the halves' own role and action slices must lie
+ * inside the batch (every row is read when the compact form is derived).  Returns 0 and the set; < 0 on an error (what
+ * cbh_batch_upload_cross refuses, except the bound on N * M); 1 = nothing was built because the set has no direct form - take
+ * cbh_batch_upload_cross, which gives the same answers (cbh_last_error says why): a table that is not flat or has derived roles,
+ * more than four actions, a principal with more than four roles, a row of the halves with more than four actions or a field
+ * that does not fit the compact record, an attribute value that needs the evaluator (an int, uint, list or map in a column a
+ * classified leaf compares: the `_any` kernels), a table with membership leaves or other conditions outside the classified
+ * leaves that is decided by the mask walk (long buckets: cbh_check_flat_kernel_any_masks has no direct form).
+ * A flat table decided by the record walks (MODE 0 / 1) whose conditions are classified leaves and membership in a list or map
+ * the request brings gets the materialised road's answers bit for bit.  If such a table ALSO holds a condition that only the
+ * evaluator call decides, the set is still served, loudly: the tuples whose answer needs that condition come back flagged
+ * (CBH_ST_UNSUPPORTED) - and the `allow` bit of a flagged tuple means NOTHING (it is 0 whatever the real answer is).  On a
+ * table that is not closed over the classified leaves always ask for `flagged` and take the flagged tuples to another road.
+ * cbh_cross_check: 0 = the planes are in the caller's memory; < 0 = an error (an empty range, r_end > M, a tile of 2^32 requests
+ * or more, words_per_plane < W, a failed allocation or copy - the set stays usable), nothing is written for a refused argument;
+ * 1 = these flags choose a plan without a direct form (CBH_F_STRICT_EVALUATION, CBH_F_WANT_EFFECTIVE_POLICIES).
+ * CBH_F_LENIENT_SCOPE_SEARCH is served.  Calls on one set queue in call order; the result words on the device are reused
+ * from tile to tile.  cbh_cross_describe: the kernel a check with these flags would launch, or "none: ..." .
+ * Not here: trails and the trace pass on a set; tables with derived roles; more than four actions; sharding over devices. */
+#define CBH_HAS_CROSS_DIRECT 1
+typedef struct cbh_cross_set cbh_cross_set;
+int cbh_cross_upload(cbh_table* t, uint32_t device_index, const cbh_batch* halves, const cbh_cross* x, cbh_cross_set** out);
+int cbh_cross_check(cbh_table* t, cbh_cross_set* set, const cbh_params* p, uint32_t r_begin, uint32_t r_end,
+                    uint64_t* allow, uint64_t* flagged, size_t words_per_plane);
+const char* cbh_cross_describe(cbh_table* t, cbh_cross_set* set, const cbh_params* p);
+void cbh_cross_release(cbh_cross_set* set);
 
 /* ---- Device-side ingest: serialized CheckInputs in, a resident batch out (the GPU flattens) ----------------------
  * The reference decodes each CheckInput and builds its request view on the CPU (internal/ruletable/check.go:536-554); so did

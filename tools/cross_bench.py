@@ -4,6 +4,8 @@
   host leg    what a caller had before cbh_batch_upload_cross: cross_product_batch (numpy lays out N * M rows on the host) +
               Table.upload (all N * M rows cross the link) + launch + download(want=()) (one byte per tuple back)
   device leg  upload_cross (N + M rows up, the device expands them) + launch + download_allow_bits (one bit per tuple back)
+  direct leg  cross_upload (N + M rows up, nothing expanded) + CrossSet.check over all M resources (one bit per tuple back, as planes);
+              timed ALTERNATING with the device leg, repetition by repetition, in the same process
 
 per configuration: 3 warm-ups, then at least 10 timed repetitions of each leg, wall clock from a synchronised device to the last
 byte on the host; min / median / max in decisions per second.  Plus the launch alone for both batches (the resident batch is the
@@ -16,6 +18,8 @@ same, so it must not differ).
                                                    ONE device leg and nothing else, for a kernel trace (rocprofv3 --kernel-trace --stats
                                                    -- python tools/cross_bench.py --profile ...); prints the bytes the expansion
                                                    and cbh_compact_pack_kernel write, to be divided by the trace's kernel times
+  python tools/cross_bench.py --profile-direct c2:4096:1024
+                                                   ONE direct leg and nothing else, for a kernel trace
 One JSON line per configuration on stdout."""
 import argparse
 import json
@@ -98,6 +102,27 @@ def device_leg(lt, table, fl, p, r, a):
     return body
 
 
+def direct_leg(lt, table, fl, p, r, a):
+    def body():
+        cs = cross.cross_direct_upload(table, fl, lt.columns, p, r, a)
+        if cs is None:
+            raise SystemExit("the set has no direct form")
+        cs.check(0, len(r), now_ns=NOW)
+        return cs
+    return body
+
+
+def timed_alternating(table, reps, warmup, bodies):
+    """the bodies in turn, repetition by repetition: what drifts over the run (clocks, the pool) drifts for all of them"""
+    out = [[] for _ in bodies]
+    for k in range(warmup + reps):
+        for i, body in enumerate(bodies):
+            dt = timed(table, 1, 0, body)[0]
+            if k >= warmup:
+                out[i].append(dt)
+    return out
+
+
 def launch_alone(table, db, reps, warmup):
     def body():
         table.launch(db, now_ns=NOW)
@@ -111,10 +136,21 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--configs", default="c2:1024:1024,c2:4096:1024,t:1024:1024,t:4096:1024")
     ap.add_argument("--profile", default=None, metavar="NAME:N:M")
+    ap.add_argument("--profile-direct", default=None, metavar="NAME:N:M")
     args = ap.parse_args()
     if args.reps < 10:
         ap.error("at least 10 timed repetitions")
     capi.init(0)
+    if args.profile_direct:
+        name, n, m = args.profile_direct.split(":")
+        n, m = int(n), int(m)
+        lt, table, fl, p, r, a = setup(name, n, m)
+        cs = direct_leg(lt, table, fl, p, r, a)()
+        print(json.dumps({"profile_direct": args.profile_direct, "kernel": cs.describe(), "columns": len(lt.columns),
+                          "plane_bytes_written": len(a) * ((n * m + 63) // 64) * 8}))
+        cs.close()
+        table.close()
+        return
     if args.profile:
         name, n, m = args.profile.split(":")
         n, m = int(n), int(m)
@@ -144,7 +180,16 @@ def main():
         line["host_batch_launch_alone"] = stats(launch_alone(table, hb, args.reps, args.warmup), decisions)
         hb.close()
         if not args.host_only:
-            line["device_leg"] = stats(timed(table, args.reps, args.warmup, device_leg(lt, table, fl, p, r, a)), decisions)
+            dev_t, dir_t = timed_alternating(table, args.reps, args.warmup, [device_leg(lt, table, fl, p, r, a), direct_leg(lt, table, fl, p, r, a)])
+            line["device_leg"] = stats(dev_t, decisions)
+            line["direct_leg"] = stats(dir_t, decisions)
+            cs = cross.cross_direct_upload(table, fl, lt.columns, p, r, a)
+            line["direct_kernel"] = cs.describe()
+
+            def check_alone():
+                cs.check(0, m, now_ns=NOW)
+            line["direct_check_alone"] = stats(timed(table, args.reps, args.warmup, check_alone), decisions)
+            cs.close()
             db = cross.cross_product_upload(table, fl, lt.columns, p, r, a)
             line["device_batch_plan"] = table.plan(db)
             line["device_batch_launch_alone"] = stats(launch_alone(table, db, args.reps, args.warmup), decisions)
