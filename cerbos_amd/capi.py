@@ -20,6 +20,8 @@ F_LENIENT_SCOPE_SEARCH = 1
 F_STRICT_EVALUATION = 2
 F_WANT_DERIVED_ROLES = 4
 F_WANT_EFFECTIVE_POLICIES = 8
+CX_DERIVED_ROLES, CX_ACTION_GROUPS = 1, 2        # cbh_cross_upload_ex `accept`
+CX_ALL = CX_DERIVED_ROLES | CX_ACTION_GROUPS
 
 EFFECT_ALLOW, EFFECT_DENY = 1, 2
 ST_OK, ST_CEL_ERROR, ST_UNSUPPORTED, ST_WANTS_TRACE = 0, 1, 2, 3
@@ -38,7 +40,7 @@ EXPORTED_SYMBOLS = [
     "cbh_wire_flatten_requests", "cbh_wire_check_requests_pb", "cbh_wire_check_requests_trail_pb", "cbh_batch_set_trail", "cbh_trail_download",
     "cbh_table_num_policies", "cbh_table_policy_key", "cbh_check_batch_trail",
     "cbh_batch_upload_cross", "cbh_result_download_allow_bits",
-    "cbh_cross_upload", "cbh_cross_check", "cbh_cross_describe", "cbh_cross_release",
+    "cbh_cross_upload", "cbh_cross_check", "cbh_cross_describe", "cbh_cross_release", "cbh_cross_upload_ex", "cbh_cross_pairs_upload",
 ]
 
 
@@ -210,6 +212,11 @@ def load():
         lib.cbh_cross_describe.restype = C.c_char_p
         lib.cbh_cross_release.argtypes = [vp]
         lib.cbh_cross_release.restype = None
+    if hasattr(lib, "cbh_cross_upload_ex"):
+        lib.cbh_cross_upload_ex.argtypes = [vp, u32, C.POINTER(CBatch), C.POINTER(CCross), u32, C.POINTER(vp)]
+        lib.cbh_cross_upload_ex.restype = i32
+        lib.cbh_cross_pairs_upload.argtypes = [vp, vp, vp, vp, u32, C.POINTER(vp)]
+        lib.cbh_cross_pairs_upload.restype = i32
     _lib = lib
     return lib
 
@@ -441,10 +448,12 @@ class Table:
         nm = int(n_principals) * int(n_resources)
         return DeviceBatch(self, h, nm * int(act.size), nm)
 
-    def cross_upload(self, halves_batch, n_principals, n_resources, action_ids, p_order=None, r_order=None, device_index=0):
-        """``cbh_cross_upload``: the same arguments as ``upload_cross``, but nothing is materialised - the device keeps the
+    def cross_upload(self, halves_batch, n_principals, n_resources, action_ids, p_order=None, r_order=None, device_index=0, accept=0):
+        """``cbh_cross_upload_ex``: the same arguments as ``upload_cross``, but nothing is materialised - the device keeps the
         ``n_principals`` + ``n_resources`` rows and ``CrossSet.check`` decides tiles of resources straight from them.  Returns the
-        ``CrossSet``, or None where the set has no direct form (return value 1: take ``upload_cross``, which gives the same answers)."""
+        ``CrossSet``, or None where the set has no direct form (return value 1: take ``upload_cross``, which gives the same answers).
+        ``accept``: ``CX_DERIVED_ROLES`` | ``CX_ACTION_GROUPS`` (``CX_ALL``) - the sets beyond ``cbh_cross_upload``'s the caller is
+        prepared for; 0 is ``cbh_cross_upload`` itself."""
         cb = make_cbatch(halves_batch, self.num_columns)
         act = np.ascontiguousarray(action_ids, dtype=np.uint32)
         po = None if p_order is None else np.ascontiguousarray(p_order, dtype=np.uint32)
@@ -454,7 +463,10 @@ class Table:
         x = CCross(n_principals, n_resources, act.size, act.ctypes.data if act.size else None,
                    po.ctypes.data if po is not None and po.size else None, ro.ctypes.data if ro is not None and ro.size else None)
         h = C.c_void_p()
-        rc = load().cbh_cross_upload(self.h, device_index, C.byref(cb), C.byref(x), C.byref(h))
+        if accept:
+            rc = load().cbh_cross_upload_ex(self.h, device_index, C.byref(cb), C.byref(x), accept, C.byref(h))
+        else:
+            rc = load().cbh_cross_upload(self.h, device_index, C.byref(cb), C.byref(x), C.byref(h))
         if rc == 1:
             return None
         _check(rc)
@@ -723,6 +735,18 @@ class CrossSet:
             raise DirectFormUnavailable(load().cbh_last_error().decode("utf-8", "replace"))
         _check(rc)
         return allow[:, :w], (flagged[:, :w] if flagged is not None else None)
+
+    def pairs_batch(self, pair_p, pair_r):
+        """``cbh_cross_pairs_upload``: the resident batch (``DeviceBatch``) of the chosen pairs x the set's actions, built on the
+        device from the set's rows - request q pairs device principal ``pair_p[q]`` with device resource ``pair_r[q]`` (what
+        ``cross.flagged_pairs`` returns).  ``Table.launch`` / ``download`` / ``set_trail`` take it; results are in the lists' order."""
+        pp, pr = np.ascontiguousarray(pair_p, dtype=np.uint32), np.ascontiguousarray(pair_r, dtype=np.uint32)
+        if pp.ndim != 1 or pp.shape != pr.shape:
+            raise ValueError("pair_p and pair_r must be two lists of one length")
+        h = C.c_void_p()
+        _check(load().cbh_cross_pairs_upload(self.table.h, self.h, pp.ctypes.data if pp.size else None, pr.ctypes.data if pr.size else None,
+                                             pp.size, C.byref(h)))
+        return DeviceBatch(self.table, h, int(pp.size) * self.shape[2], int(pp.size))
 
     def describe(self, flags=0):
         """The kernel a ``check`` with these flags would launch (``cbh_cross_describe``), or "none: ..." ."""

@@ -116,18 +116,19 @@ def upload_halves(table, halves, n, m, act_ids, p_order, r_order, device_index=0
 
 
 def cross_direct_upload(table, flattener, columns, principals, resources, actions, aux_data=None,
-                        default_policy_version="default", default_scope="", sort=True, device_index=0):
+                        default_policy_version="default", default_scope="", sort=True, device_index=0, accept=0):
     """``cross_product_upload`` without the product (``capi.Table.cross_upload``): the device keeps the N + M halves and
     ``capi.CrossSet.check`` decides tiles of resources straight from them - N * M is bounded by what the caller wants back, not by
     device memory.  Returns the ``capi.CrossSet`` with ``shape``, ``p_order``, ``r_order`` (``allow_cube_planes`` accepts it), or
-    None where the set has no direct form: take ``cross_product_upload``, which gives the same answers."""
+    None where the set has no direct form: take ``cross_product_upload``, which gives the same answers.  ``accept``:
+    ``capi.CX_DERIVED_ROLES`` | ``capi.CX_ACTION_GROUPS`` - tables with derived roles, more than four actions; by default neither."""
     h, p_order, r_order, act_ids = cross_halves(flattener, principals, resources, actions, aux_data, default_policy_version, default_scope, sort)
-    return direct_upload_halves(table, h, len(principals), len(resources), act_ids, p_order, r_order, device_index)
+    return direct_upload_halves(table, h, len(principals), len(resources), act_ids, p_order, r_order, device_index, accept)
 
 
-def direct_upload_halves(table, halves, n, m, act_ids, p_order, r_order, device_index=0):
+def direct_upload_halves(table, halves, n, m, act_ids, p_order, r_order, device_index=0, accept=0):
     """``cross_direct_upload`` for halves that are flattened already; an order of None is the identity."""
-    cs = table.cross_upload(halves, n, m, act_ids, p_order, r_order, device_index=device_index)
+    cs = table.cross_upload(halves, n, m, act_ids, p_order, r_order, device_index=device_index, accept=accept)
     if cs is not None:
         cs.p_order = np.arange(n) if p_order is None else np.asarray(p_order)
         cs.r_order = np.arange(m) if r_order is None else np.asarray(r_order)
@@ -146,6 +147,21 @@ def allow_cube_planes(cross_set, r_begin, r_end, planes):
     out = np.empty((n, mt, a), dtype=bool)
     out[np.ix_(cross_set.p_order, np.argsort(np.argsort(res)))] = dev.transpose(2, 1, 0)
     return out
+
+
+def flagged_pairs(cross_set, r_begin, r_end, flagged):
+    """``flagged`` planes of ``capi.CrossSet.check(r_begin, r_end, want_flagged=True)`` -> (pair_p, pair_r, action_mask): the pairs of
+    the tile with a flagged action, in DEVICE order (ascending bit index: resource-major) - ``pair_r = r_begin + q // n``,
+    ``pair_p = q % n``, what ``capi.CrossSet.pairs_batch`` takes - and per pair a uint64 with bit k set = action k is flagged."""
+    n, _, a = cross_set.shape
+    nt = n * (r_end - r_begin)
+    by = np.ascontiguousarray(flagged, dtype="<u8").view(np.uint8).reshape(a, -1)
+    bits = np.unpackbits(by, axis=1, count=nt, bitorder="little").astype(bool)          # [k][q]
+    q = np.flatnonzero(bits.any(axis=0))
+    mask = np.zeros(q.size, dtype=np.uint64)
+    for k in range(a):
+        mask |= bits[k, q].astype(np.uint64) << np.uint64(k)
+    return (q % n).astype(np.uint32), (r_begin + q // n).astype(np.uint32), mask
 
 
 def allow_cube(batch, bits):

@@ -448,9 +448,13 @@ __device__ __forceinline__ u64 load_u64g(const CBH_G u32* p) {   // 8-byte align
 // principal's record, kind, version and scope from the resource's, the actions from the launch (the same for every lane), the
 // columns from either row by their side (cc_fill_cross).  The walk and the fold are the same; no result word is written - one
 // ballot per action (and one of "status is not OK", where wanted) is stored by the wave's first lane.
+// CROSS with MEMO (cbh_check_flat_kernel_dr_x, a table with derived roles): the memo needs nothing of its own here.  A reference is
+// wave-uniform as before (a record's, a scope's definition's); on a miss the outcome is computed for EVERY lane - each lane has its
+// pair's two rows in its slice of the column cache, and a lane beyond the tile's end shadows pair 0 with no role and no action, so
+// what the memo keeps for it is a real pair's outcome that nothing reads.
 template <bool WITH_CALL, int MODE, bool EP = false, bool MEMO = false, bool COMPACT = false, bool CROSS = false>
 __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c, const CrossDev& x = CrossDev{}) {
-  static_assert(!CROSS || (COMPACT && !WITH_CALL && !EP && !MEMO), "the direct cross form: compact inputs, no evaluator call, no trail, no memo");
+  static_assert(!CROSS || (COMPACT && !WITH_CALL && !EP), "the direct cross form: compact inputs, no evaluator call, no trail");
   constexpr bool STAGED = MODE == 1;
   constexpr u32 BTYPE = MODE == 2 ? (u32)CBH_B_RESSEG : (u32)CBH_B_RESOURCE;
   const TableDev& t = ka_regs.t;
@@ -1351,7 +1355,8 @@ static inline bool cbh_is_flat_compact_kernel(cbh_check_kernel_fn fn) {
   return fn == cbh_check_flat_kernel_c || fn == cbh_check_flat_kernel_staged_c || fn == cbh_check_flat_kernel_masks_c;
 }
 // The direct cross road's instantiations (flat_body CROSS; cerbos_hip.h cbh_cross_check): MODE 0, 1, 2 without the evaluator call, the
-// cross arguments a by-value parameter of their own.  Same attributes as their compact siblings.
+// cross arguments a by-value parameter of their own.  Same attributes as their compact siblings.  A set of more than four actions is
+// decided by several launches of the same kernel, four actions each (cbh_host_resident.h cross_set_check): nothing here knows.
 __global__ CBH_FLAT_ATTRS(7) void cbh_check_flat_kernel_x(const KernelArgs a, const KernelArgs* __restrict__ ka, const CrossDev x) {
   CBH_FLAT_CTX_C(a, ka);
   flat_body<false, 0, false, false, true, true>(a, c, x);
@@ -1364,25 +1369,36 @@ __global__ CBH_FLAT_ATTRS(4) void cbh_check_flat_kernel_masks_x(const KernelArgs
   CBH_FLAT_CTX_C(a, ka);
   flat_body<false, 2, false, false, true, true>(a, c, x);
 }
+// ... and MODE 0 with the memo of condition outcomes, for a table with derived roles (cbh_check_flat_kernel_dr's direct sibling): 72 VGPRs,
+// seven waves, no scratch - the compact prologue that spilled two registers beside the memo in a `_dr_c` does not in this form - and
+// C3 4096 x 1024 3.4 % faster than on the plain `_x` (profiles/cross_direct_dr.txt)
+__global__ CBH_FLAT_ATTRS(7) void cbh_check_flat_kernel_dr_x(const KernelArgs a, const KernelArgs* __restrict__ ka, const CrossDev x) {
+  CBH_FLAT_CTX_C(a, ka);
+  flat_body<false, 0, false, true, true, true>(a, c, x);
+}
 typedef void (*cbh_cross_kernel_fn)(const KernelArgs, const KernelArgs*, const CrossDev);
-// The direct instantiation of the kernel a plan picks, by its MODE, or null where it has none (the derived-role variant, the trail's,
-// the mask walk with the call).  A table that is not closed over the classified leaves is planned an `_any` kernel even for a batch of
+// The direct instantiation of the kernel a plan picks, by its MODE (3: MODE 0 with the memo), or null where it has none (the trail's,
+// the mask walk with the call).  A derived-role table's staged and mask plans are the ordinary kernels (cbh_pick_kernel), so their
+// direct siblings are the ordinary ones too.  CBH_CROSS_DR_MEMO=0 (measurement aid): cbh_check_flat_kernel_dr -> the plain `_x`.
+// A table that is not closed over the classified leaves is planned an `_any` kernel even for a batch of
 // plain tags (the host refuses the other batches).  For MODE 0 and 1 its direct sibling is the same instantiation: there every
 // condition goes through `leafish`, which in a CROSS instantiation decides the membership leaves inline and marks what only the
 // evaluator call could decide UNSUPPORTED, which the caller sees in the `flagged` planes.  NOT for MODE 2: the mask walk evaluates
 // leaves in blocks (leaf_block_codes) that know classes 1-4 and 6 only - a membership leaf there would make every candidate of its
 // segment UNSUPPORTED - so cbh_check_flat_kernel_any_masks has no direct form and the set takes the materialised road.
 static inline int cbh_flat_cross_mode(cbh_check_kernel_fn fn) {
+  static const char* memo = getenv("CBH_CROSS_DR_MEMO");
+  if (fn == cbh_check_flat_kernel_dr) return (memo && *memo == '0') ? 0 : 3;
   return (fn == cbh_check_flat_kernel || fn == cbh_check_flat_kernel_any) ? 0 : (fn == cbh_check_flat_kernel_staged || fn == cbh_check_flat_kernel_any_staged) ? 1
        : fn == cbh_check_flat_kernel_masks ? 2 : -1;
 }
 static inline cbh_cross_kernel_fn cbh_flat_cross_variant(cbh_check_kernel_fn fn) {
   const int m = cbh_flat_cross_mode(fn);
-  return m == 0 ? cbh_check_flat_kernel_x : m == 1 ? cbh_check_flat_kernel_staged_x : m == 2 ? cbh_check_flat_kernel_masks_x : nullptr;
+  return m == 0 ? cbh_check_flat_kernel_x : m == 1 ? cbh_check_flat_kernel_staged_x : m == 2 ? cbh_check_flat_kernel_masks_x : m == 3 ? cbh_check_flat_kernel_dr_x : nullptr;
 }
 static inline const char* cbh_flat_cross_name(cbh_check_kernel_fn fn) {
   const int m = cbh_flat_cross_mode(fn);
-  return m == 0 ? "cbh_check_flat_kernel_x" : m == 1 ? "cbh_check_flat_kernel_staged_x" : m == 2 ? "cbh_check_flat_kernel_masks_x" : "";
+  return m == 0 ? "cbh_check_flat_kernel_x" : m == 1 ? "cbh_check_flat_kernel_staged_x" : m == 2 ? "cbh_check_flat_kernel_masks_x" : m == 3 ? "cbh_check_flat_kernel_dr_x" : "";
 }
 #define CBH_FLAT_STAGE_MIN 32u
 // the mask walk decides a table that has segments and long buckets (CBH_FLAT_MASKS=0: never, =1: whatever the buckets' length - tests, A/B)

@@ -1,6 +1,7 @@
 // Cross-product batches built on the device (cerbos_hip.h cbh_batch_upload_cross) and the allow bitmap of a resident batch
 // (cbh_result_download_allow_bits).  Three small kernels, none of them on the decision path: the product they build is an ordinary
-// resident batch the decision kernels read unchanged.  And the one-lane kernel of the DIRECT road (cbh_cross_upload), which
+// resident batch the decision kernels read unchanged.  And the two kernels of the DIRECT road (cbh_cross_upload_ex) - the one lane that
+// writes the action words, and the gather that turns chosen pairs of a set into a resident batch (cbh_cross_pairs_upload) -, which
 // materialises no product: its decision kernels are the flat kernels' CROSS instantiations (cbh_check_flat.h), which read the
 // halves' compact form in place and write ballots.
 //
@@ -82,17 +83,57 @@ __global__ __launch_bounds__(256) void cbh_allow_bits_kernel(AllowBitsArgs a) {
   if ((threadIdx.x & 63u) == 0u && k < a.n_tuples) a.bits[k >> 6] = mask;
 }
 
-// The direct road's action word (CrossDev.act_word): the classes of the A <= 4 actions every request asks for, by the expressions of
-// cbh_compact_pack_kernel (clamps included), five bits each as in word 3 of a compact record, and A << 20.  One lane, once per upload.
+// The direct road's action words (CrossDev.act_word), one per group of four actions (a set of A actions is decided in (A + 3) / 4
+// launches, group g = the actions 4 g .. 4 g + 3): the classes of the group's actions, by the expressions of cbh_compact_pack_kernel
+// (clamps included), five bits each as in word 3 of a compact record, and the group's action count << 20.  One lane, once per upload.
 struct CrossActWordArgs { const CBH_G u32* action_ids; const CBH_G u8* action_class; CBH_G u32* out; u32 a, K; };
 __global__ __launch_bounds__(64) void cbh_cross_act_word_kernel(CrossActWordArgs x) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
   const u32 kmax = x.K ? x.K - 1u : 0u;
-  u32 w = x.a << 20;
-  for (u32 k = 0; k < 4; ++k) {
-    const u32 aid = x.action_ids[k < x.a ? k : 0u];
-    const u32 ca = x.K ? x.action_class[aid < x.K ? aid : kmax] : 31u;
-    w |= ((k < x.a && aid < x.K && ca < 31u) ? ca : 31u) << (5u * k);
+  for (u32 g = 0; 4u * g < x.a; ++g) {
+    const u32 cnt = x.a - 4u * g < 4u ? x.a - 4u * g : 4u;
+    u32 w = cnt << 20;
+    for (u32 k = 0; k < 4; ++k) {
+      const u32 aid = x.action_ids[4u * g + (k < cnt ? k : 0u)];
+      const u32 ca = x.K ? x.action_class[aid < x.K ? aid : kmax] : 31u;
+      w |= ((k < cnt && aid < x.K && ca < 31u) ? ca : 31u) << (5u * k);
+    }
+    x.out[g] = w;
   }
-  x.out[0] = w;
+}
+
+// Chosen pairs of a direct set as an ordinary resident batch (cerbos_hip.h cbh_cross_pairs_upload): cbh_cross_expand_kernel for a LIST of
+// pairs.  Request q pairs device principal pair_p[q] with device resource pair_r[q] - the set's own orders, what a tile's bit index
+// decodes to - instead of dividing q; the host has checked every index against n and m before the launch.  One lane per pair; the
+// loads gather from the N + M rows (which stay in cache), every store goes to [field or column][q].  cbh_cross_actions_kernel then
+// fills tuple_action as for a product of n_pairs x 1.
+struct CrossGatherArgs {
+  const CBH_G u32* h_req; const CBH_G u8* h_tag; const CBH_G u64* h_val;   // the set's halves: [CBH_RQ_NFIELDS][nh], [n_columns][nh], [n_columns][nh]
+  const CBH_G u32* p_order; const CBH_G u32* r_order;                      // [n], [nh - n], or null = identity
+  const CBH_G u8* col_side;                                                // [n_columns]
+  const CBH_G u32* pair_p; const CBH_G u32* pair_r;                        // [n_pairs] device indices, < n and < nh - n
+  CBH_G u32* req; CBH_G u8* tag; CBH_G u64* val;                           // the batch: [CBH_RQ_NFIELDS][n_pairs], [n_columns][n_pairs] twice
+  u32 n, nh, n_pairs, a, n_columns, pad;
+};
+__global__ __launch_bounds__(256) void cbh_cross_gather_kernel(CrossGatherArgs x) {
+  const u64 q64 = (u64)blockIdx.x * 256u + threadIdx.x;
+  if (q64 >= x.n_pairs) return;
+  const u32 q = (u32)q64;
+  const u32 ip = x.pair_p[q], jp = x.pair_r[q];
+  const size_t NH = x.nh, NP = x.n_pairs;
+  const size_t pi = x.p_order ? x.p_order[ip] : ip;
+  const size_t ri = (size_t)x.n + (x.r_order ? x.r_order[jp] : jp);
+#pragma unroll
+  for (u32 f = 0; f < CBH_RQ_NFIELDS; ++f) {
+    u32 v;
+    if (f == CBH_RQ_ACT_OFF) v = q * x.a;
+    else if (f == CBH_RQ_ACT_CNT) v = x.a;
+    else v = x.h_req[f * NH + (((CBH_CROSS_R_FIELDS >> f) & 1u) ? ri : pi)];
+    x.req[f * NP + q] = v;
+  }
+  for (u32 c = 0; c < x.n_columns; ++c) {
+    const size_t src = c * NH + (x.col_side[c] ? ri : pi);
+    x.tag[c * NP + q] = x.h_tag[src];
+    x.val[c * NP + q] = x.h_val[src];
+  }
 }

@@ -200,7 +200,8 @@ extern "C" int cbh_batch_upload(cbh_table* t, const cbh_batch* in, cbh_device_ba
 // The batch's shape comes from the halves, looking only at the rows the product uses, so that the product gets the plan a
 // host-built batch of the same requests gets (validate_batch's answers for that batch, without the batch).
 // (`bounded`: the product is materialised, so N * M and N * M * A must stay below 2^32 - the direct road, cbh_cross_upload, has no such bound)
-struct CrossShape { std::vector<u8> side; u32 maxr = 0, wide_lo = 0, wide_hi = 0; bool plain = true; };
+// (`plan_a`, set by the caller: the action count the plan is made for where it is not A - the direct road decides A > 4 four at a time)
+struct CrossShape { std::vector<u8> side; u32 maxr = 0, wide_lo = 0, wide_hi = 0; bool plain = true; u32 plan_a = 0; };
 static int cross_validate(cbh_table* t, uint32_t device_index, const cbh_batch* h, const cbh_cross* x, bool bounded, CrossShape& cs) {
   if (device_index >= t->reps.size()) return fail("device index out of range");
   const u64 N = x->n_principals, M = x->n_resources, A = x->n_actions;
@@ -245,7 +246,7 @@ static int cross_validate(cbh_table* t, uint32_t device_index, const cbh_batch* 
   bool plain = true;
   {
     const u32 mf = t->meta[CBH_M_FLAGS];
-    const bool matters = ((mf & CBH_MF_FLAT) && A <= 4 && maxr <= 4) || ((mf & CBH_MF_WALK2) && t->meta[CBH_M_GSLOTS_ALL] > t->meta[CBH_M_GSLOTS_GENERIC]);
+    const bool matters = ((mf & CBH_MF_FLAT) && (cs.plan_a ? cs.plan_a : A) <= 4 && maxr <= 4) || ((mf & CBH_MF_WALK2) && t->meta[CBH_M_GSLOTS_ALL] > t->meta[CBH_M_GSLOTS_GENERIC]);
     u32 sens = t->meta[CBH_M_SENS_COLS];
     if (ncol < 32) sens &= (1u << ncol) - 1u;
     bool hit = false;
@@ -633,71 +634,100 @@ extern "C" int cbh_result_download_allow_bits(cbh_table* t, cbh_device_batch* b,
 }
 
 
-// ---- the direct cross road: N x M decided straight from the N + M halves (cerbos_hip.h cbh_cross_upload / cbh_cross_check) ----
+// ---- the direct cross road: N x M decided straight from the N + M halves (cerbos_hip.h cbh_cross_upload_ex / cbh_cross_check) ----
 // The set is the HALVES as a resident batch in its compact form (batch_upload + batch_compact, unchanged: the device holds N + M
-// rows), the two orders, the columns' sides as a mask and the actions' classes as one word.  A check launches the `_x` sibling of
-// the kernel plan_for picks for (A actions, the principals' roles, plain tags) with the compact launch's LDS, over the tile's
-// N * (r_end - r_begin) pairs; what comes back is one ballot word per 64 pairs and action.  The planes' device words belong to the
-// set's batch (the replica's pool) and serve every tile that fits them.
+// rows, the wide arrays included - cbh_cross_pairs_upload gathers from them), the two orders, the columns' sides and the actions'
+// classes as one word per group of four.  A check launches the `_x` sibling of the kernel plan_for picks for (min(A, 4) actions,
+// the principals' roles, plain tags) with the compact launch's LDS, over the tile's N * (r_end - r_begin) pairs - once per group
+// of four actions, on the set's stream, each launch writing its own planes; what comes back is one ballot word per 64 pairs and
+// action.  The planes' device words belong to the set's batch (the replica's pool) and serve every tile that fits them.
 struct cbh_cross_set {
   cbh_device_batch* b = nullptr;
   u32 n = 0, m = 0, a = 0, maxr = 0; bool plain = true;
   const u32* p_order = nullptr; const u32* r_order = nullptr;   // device, or null = identity
-  u32 side = 0, act_word = 0;
+  u32 side = 0;                                                   // the cached columns' sides as a mask (CrossDev.side)
+  std::vector<u32> act_words;                                     // one per group of four actions (cbh_cross_act_word_kernel)
   u64* planes = nullptr; size_t plane_cap = 0;   // [allow | flagged][a][words]
+  // what cbh_cross_pairs_upload needs beside the halves' own arrays: every column's side and the action ids on the device, the
+  // principals' role counts by device position (the shape of a batch of chosen pairs), the length of the strings' bytes
+  const u8* d_side = nullptr; const u32* d_act = nullptr;
+  std::vector<u8> p_roles; u32 str_bytes_len = 0;
 };
+static u32 cross_groups(const cbh_cross_set* cs) { return (cs->a + 3u) / 4u; }
 static cbh_cross_kernel_fn cross_kernel_for(const cbh_cross_set* cs, u32 eval_flags, CbhPlan& pl) {
-  pl = plan_for(cs->b->rep->dev, cs->a, cs->maxr, cs->plain, eval_flags & ~(u32)CBH_FI_MASK);
+  pl = plan_for(cs->b->rep->dev, std::min(cs->a, 4u), cs->maxr, cs->plain, eval_flags & ~(u32)CBH_FI_MASK);
   if (pl.kind != 1 || (eval_flags & CBH_F_DEBUG_CYCLES)) return nullptr;
   return cbh_flat_cross_variant(pl.kernel);
 }
-static int cross_set_upload(cbh_table* t, uint32_t device_index, const cbh_batch* h, const cbh_cross* x, cbh_cross_set** out) {
+static int cross_set_upload(cbh_table* t, uint32_t device_index, const cbh_batch* h, const cbh_cross* x, uint32_t accept, cbh_cross_set** out) {
   if (out) *out = nullptr;
   if (!t || !h || !x || !out) return fail("null argument");
+  if (accept & ~(uint32_t)(CBH_CX_DERIVED_ROLES | CBH_CX_ACTION_GROUPS)) return fail("cbh_cross_upload_ex: `accept` has a bit this library does not know");
   CrossShape shape;
+  shape.plan_a = std::min(x->n_actions, 4u);
   if (cross_validate(t, device_index, h, x, false, shape) != 0) return -1;
   Replica* rep = t->reps[device_index];
   const u32 N = x->n_principals, M = x->n_resources, A = x->n_actions;
   // no direct form: the caller takes cbh_batch_upload_cross, which gives the same answers
   if (!(rep->dev.flags & CBH_MF_FLAT)) { g_err = "cbh_cross_upload: no direct form - the table is not flat"; return 1; }
-  if (rep->dev.n_dr) { g_err = "cbh_cross_upload: no direct form - the table has derived roles"; return 1; }
-  if (A > 4) { g_err = "cbh_cross_upload: no direct form - more than four actions"; return 1; }
+  if (rep->dev.n_dr && !(accept & CBH_CX_DERIVED_ROLES)) { g_err = "cbh_cross_upload: no direct form - the table has derived roles"; return 1; }
+  if (A > 4 && !(accept & CBH_CX_ACTION_GROUPS)) { g_err = "cbh_cross_upload: no direct form - more than four actions"; return 1; }
   if (shape.maxr > 4) { g_err = "cbh_cross_upload: no direct form - a principal has more than four roles"; return 1; }
   if (!shape.plain) { g_err = "cbh_cross_upload: no direct form - an attribute value needs the evaluator (int / uint / list / map in a sensitive column)"; return 1; }
   if (!compact_inputs_on()) { g_err = "cbh_cross_upload: no direct form - compact inputs are switched off"; return 1; }
   {   // the kernel the product would be planned (mask walk of a table that is not closed over the classified leaves: cbh_flat_cross_mode)
-    const CbhPlan pl = plan_for(rep->dev, A, shape.maxr, shape.plain, 0);
+    const CbhPlan pl = plan_for(rep->dev, shape.plan_a, shape.maxr, shape.plain, 0);
     if (pl.kind != 1 || !cbh_flat_cross_variant(pl.kernel)) { g_err = "cbh_cross_upload: no direct form - the kernel planned for this table has no direct instantiation"; return 1; }
   }
   cbh_cross_set* cs = new (std::nothrow) cbh_cross_set();
   if (!cs) return fail("out of memory");
-  cs->n = N; cs->m = M; cs->a = A; cs->maxr = shape.maxr; cs->plain = shape.plain;
+  cs->n = N; cs->m = M; cs->a = A; cs->maxr = shape.maxr; cs->plain = shape.plain; cs->str_bytes_len = h->str_bytes_len;
   for (u32 c = 0; c < h->n_columns && c < CBH_CACHE_COLS; ++c) if (shape.side[c]) cs->side |= 1u << c;
+  const size_t NH = (size_t)N + M;
+  cs->p_roles.resize(N);
+  for (u32 ip = 0; ip < N; ++ip) cs->p_roles[ip] = (u8)h->req_u32[(size_t)CBH_RQ_ROLE_CNT * NH + (x->p_order ? x->p_order[ip] : ip)];   // (<= 4: checked above)
+  // The halves' OWN actions are not read by any road of a set, but a row that carries more than four of them has no compact
+  // record (cbh_compact_scan_kernel) - and the flattener hands the set's A actions to the first row.  A set of action groups
+  // therefore uploads the request words with such rows' action counts cleared; a set of up to four actions is uploaded as it is.
+  cbh_batch hh = *h;
+  std::vector<u32> req_copy;
+  if (A > 4) {
+    req_copy.assign(h->req_u32, h->req_u32 + (size_t)CBH_RQ_NFIELDS * NH);
+    u32* cnt = req_copy.data() + (size_t)CBH_RQ_ACT_CNT * NH;
+    for (size_t r = 0; r < NH; ++r) if (cnt[r] > 4u && (u64)req_copy[(size_t)CBH_RQ_ACT_OFF * NH + r] + cnt[r] <= (u64)h->n_tuples) cnt[r] = 0;   // (a slice outside the batch stays, to be refused)
+    hh.req_u32 = req_copy.data();
+  }
   // the halves: an ordinary resident batch of N + M requests (validated as one: the scan and the pack read every row's role and
   // action slices) with its compact form
-  if (batch_upload(t, device_index, h, &cs->b, true) != 0) { delete cs; return -1; }
+  if (batch_upload(t, device_index, &hh, &cs->b, true) != 0) { delete cs; return -1; }
   cbh_device_batch* b = cs->b;
   auto drop = [&](int rc) { cbh_batch_release(b); delete cs; return rc; };
-  b->max_actions = A; b->max_roles = shape.maxr; b->plain_tags = shape.plain;   // (the PRODUCT's shape: what a plan is made for)
+  b->max_actions = A; b->max_roles = shape.maxr; b->plain_tags = shape.plain;   // (the PRODUCT's shape; the plan is made for min(A, 4) actions: cross_kernel_for)
   if (!b->compact) { g_err = "cbh_cross_upload: no direct form - a field of the halves does not fit the compact record (CBH_CI_MISFIT)"; return drop(1); }
   hipStream_t s = b->stream;
-  const u32* d_act = nullptr; u32* d_word = nullptr;
+  u32* d_word = nullptr;
+  const u32 G = cross_groups(cs);
+  cs->act_words.assign(G, 0u);
   int rc = 0;
   if (x->p_order) rc |= up(b, cs->p_order, x->p_order, (size_t)N, s);
   if (x->r_order) rc |= up(b, cs->r_order, x->r_order, (size_t)M, s);
-  rc |= up(b, d_act, x->action_ids, (size_t)A, s);
-  rc |= dalloc(b, d_word, 1);
+  rc |= up(b, cs->d_act, x->action_ids, (size_t)A, s);
+  rc |= up(b, cs->d_side, (const u8*)shape.side.data(), (size_t)h->n_columns, s);   // (pageable memory of this frame: the wait below)
+  rc |= dalloc(b, d_word, G);
   if (rc != 0) return drop(-1);
-  CrossActWordArgs wa{}; wa.action_ids = d_act; wa.action_class = rep->dev.action_class; wa.out = d_word; wa.a = A; wa.K = rep->dev.K;
+  CrossActWordArgs wa{}; wa.action_ids = cs->d_act; wa.action_class = rep->dev.action_class; wa.out = d_word; wa.a = A; wa.K = rep->dev.K;
   hipLaunchKernelGGL(cbh_cross_act_word_kernel, dim3(1), dim3(64), 0, s, wa);
-  if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&cs->act_word, d_word, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+  if (hipGetLastError() != hipSuccess || hipMemcpyAsync(cs->act_words.data(), d_word, (size_t)G * 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
     (void)hipGetLastError(); fail("cbh_cross_upload: upload failed"); return drop(-1);
   }
   *out = cs;
   return 0;
 }
+extern "C" int cbh_cross_upload_ex(cbh_table* t, uint32_t device_index, const cbh_batch* halves, const cbh_cross* x, uint32_t accept, cbh_cross_set** out) {
+  try { return cross_set_upload(t, device_index, halves, x, accept, out); } catch (...) { return fail("out of memory"); }
+}
 extern "C" int cbh_cross_upload(cbh_table* t, uint32_t device_index, const cbh_batch* halves, const cbh_cross* x, cbh_cross_set** out) {
-  try { return cross_set_upload(t, device_index, halves, x, out); } catch (...) { return fail("out of memory"); }
+  return cbh_cross_upload_ex(t, device_index, halves, x, 0, out);
 }
 static int cross_set_check(cbh_table* t, cbh_cross_set* cs, const cbh_params* p, uint32_t r_begin, uint32_t r_end, uint64_t* allow, uint64_t* flagged, size_t words_per_plane) {
   if (!t || !cs || !p || !allow) return fail("null argument");
@@ -735,11 +765,16 @@ static int cross_set_check(cbh_table* t, cbh_cross_set* cs, const cbh_params* p,
   ka.t = rep->dev; ka.b = b->dev; ka.now_ns = p->now_ns;
   ka.flags = (p->flags & ~(u32)CBH_FI_MASK) | CBH_FI_COMPACT | CBH_FI_PACKED_TAGS;   // (a compact launch: the cache's tags in the packed form)
   CrossDev x{};
-  x.p_order = cs->p_order; x.r_order = cs->r_order; x.allow = cs->planes; x.flagged = flagged ? cs->planes + per : nullptr;
-  x.n = cs->n; x.r_begin = r_begin; x.n_tile = (u32)nt; x.words = (u32)W; x.side = cs->side; x.act_word = cs->act_word;
+  x.p_order = cs->p_order; x.r_order = cs->r_order;
+  x.n = cs->n; x.r_begin = r_begin; x.n_tile = (u32)nt; x.words = (u32)W; x.side = cs->side;
   const TableDev& dev = rep->dev;
   const size_t lds = cbh_plan_lds(pl, dev.flags, dev.max_depth, dev.n_scopes, dev.K, ka.b.n_columns, dev.inline_cols, dev.n_dr, false, CBH_W2_NA, true) + lds_pad();
-  hipLaunchKernelGGL(fn, dim3((u32)((nt + pl.threads - 1) / pl.threads)), dim3(pl.threads), lds, s, ka, (const KernelArgs*)nullptr, x);   // (the arguments in memory are the evaluator call's: no _x kernel has one)
+  // one launch per group of four actions, each with the group's word and its own planes [4 g, 4 g + 4) of the block
+  for (u32 g = 0; g < cross_groups(cs); ++g) {
+    x.act_word = cs->act_words[g];
+    x.allow = cs->planes + (size_t)4 * g * W; x.flagged = flagged ? cs->planes + per + (size_t)4 * g * W : nullptr;
+    hipLaunchKernelGGL(fn, dim3((u32)((nt + pl.threads - 1) / pl.threads)), dim3(pl.threads), lds, s, ka, (const KernelArgs*)nullptr, x);   // (the arguments in memory are the evaluator call's: no _x kernel has one)
+  }
   HIPCHK(hipGetLastError());
   for (int which = 0; which < (flagged ? 2 : 1); ++which) {
     uint64_t* dst = which ? flagged : allow; const u64* src = cs->planes + (size_t)which * per;
@@ -759,7 +794,12 @@ extern "C" const char* cbh_cross_describe(cbh_table* t, cbh_cross_set* cs, const
     CbhPlan pl;
     if (cs->b->table != t) s = "none: the set was uploaded for a different table";
     else if (!cross_kernel_for(cs, p->flags, pl)) s = "none: these flags choose a plan without a direct form";
-    else { char m[96]; snprintf(m, sizeof m, "[direct cross, %u + %u rows, narrow columns 0x%x]", cs->n, cs->m, cs->b->dev.compact_info & CBH_CI_NARROW_MASK); s = std::string(cbh_flat_cross_name(pl.kernel)) + m; }
+    else {
+      char m[128], g[40] = "";
+      if (cross_groups(cs) > 1) snprintf(g, sizeof g, ", %u action groups", cross_groups(cs));
+      snprintf(m, sizeof m, "[direct cross, %u + %u rows, narrow columns 0x%x%s]", cs->n, cs->m, cs->b->dev.compact_info & CBH_CI_NARROW_MASK, g);
+      s = std::string(cbh_flat_cross_name(pl.kernel)) + m;
+    }
   } catch (...) { return ""; }
   return s.c_str();
 }
@@ -767,6 +807,77 @@ extern "C" void cbh_cross_release(cbh_cross_set* cs) {
   if (!cs) return;
   cbh_batch_release(cs->b);
   delete cs;
+}
+
+// Chosen pairs of a set - the flagged ones, as a rule - as an ordinary resident batch built on the device from the set's own rows
+// (cbh_cross_gather_kernel), by cross_upload's steps: the same constructor, counts, buffers and compact form, and the shape a
+// host-built batch of those requests would get.  Roles, heap and strings are copied device to device: the batch outlives the set.
+template <typename T>
+static int dcopy(cbh_device_batch* b, const T*& dst, const T* src, size_t n, hipStream_t s) {
+  T* p = nullptr; dst = nullptr;
+  if (dalloc(b, p, n) != 0) return -1;
+  if (n) HIPCHK(hipMemcpyAsync(p, src, n * sizeof(T), hipMemcpyDeviceToDevice, s));
+  dst = p;
+  return 0;
+}
+static int cross_pairs_upload(cbh_table* t, cbh_cross_set* cs, const uint32_t* pair_p, const uint32_t* pair_r, uint32_t n_pairs, cbh_device_batch** out) {
+  if (out) *out = nullptr;
+  if (!t || !cs || !pair_p || !pair_r || !out) return fail("null argument");
+  cbh_device_batch* hb = cs->b;
+  if (hb->table != t) return fail("the set was uploaded for a different table");
+  if (!n_pairs) return fail("cbh_cross_pairs_upload: n_pairs must be at least 1");
+  const u64 NP = n_pairs, A = cs->a;
+  if (NP * A >= (1ull << 32)) return fail("cbh_cross_pairs_upload: the batch has 2^32 tuples or more: take fewer pairs");
+  u32 maxr = 0;
+  for (u32 q = 0; q < n_pairs; ++q) {   // before anything is launched: the kernel indexes the set's rows with these
+    if (pair_p[q] >= cs->n || pair_r[q] >= cs->m) return fail("cbh_cross_pairs_upload: a pair's index is outside the set (pair_p < n_principals, pair_r < n_resources, device order)");
+    maxr = std::max(maxr, (u32)cs->p_roles[pair_p[q]]);
+  }
+  Replica* rep = hb->rep;
+  HIPCHK(hipSetDevice(rep->device));
+  cbh_device_batch* b = batch_new(t, rep, false);
+  if (!b) return -1;
+  const BatchDev& hd = hb->dev;
+  const u32 ncol = hd.n_columns;
+  b->max_actions = (u32)A; b->max_roles = maxr; b->plain_tags = cs->plain;   // (every row of a set holds plain values)
+  b->wide_lo = 0; b->wide_hi = A > CBH_W2_NA ? n_pairs : 0;                  // (no principal of a set has more than four roles)
+  BatchDev& d = b->dev;
+  batch_set_counts(b, n_pairs, (u32)(NP * A), hd.n_roles, ncol, hd.n_strings, hd.heap_len);
+  hipStream_t s = b->stream;
+  CrossGatherArgs ga{};
+  ga.h_req = hd.req_u32; ga.h_tag = hd.col_tag; ga.h_val = hd.col_val; ga.p_order = cs->p_order; ga.r_order = cs->r_order; ga.col_side = cs->d_side;
+  ga.n = cs->n; ga.nh = cs->n + cs->m; ga.n_pairs = n_pairs; ga.a = (u32)A; ga.n_columns = ncol;
+  CrossArgs ca{};   // (for cbh_cross_actions_kernel: a product of n_pairs x 1)
+  ca.n = n_pairs; ca.m = 1; ca.a = (u32)A; ca.action_ids = cs->d_act;
+  int rc = 0;
+  rc |= up(b, ga.pair_p, pair_p, (size_t)n_pairs, s);
+  rc |= up(b, ga.pair_r, pair_r, (size_t)n_pairs, s);
+  rc |= dcopy(b, d.roles, hd.roles, hd.n_roles, s);
+  rc |= dcopy(b, d.heap_tag, hd.heap_tag, hd.heap_len, s);
+  rc |= dcopy(b, d.heap_val, hd.heap_val, hd.heap_len, s);
+  rc |= dcopy(b, d.str_off, hd.str_off, hd.n_strings ? (size_t)hd.n_strings + 1 : 0, s);
+  rc |= dcopy(b, d.str_bytes, hd.str_bytes, cs->str_bytes_len, s);
+  rc |= dcopy(b, d.str_flags, hd.str_flags, hd.n_strings, s);
+  d.tuple_req = nullptr;
+  rc |= dalloc(b, ga.req, (size_t)CBH_RQ_NFIELDS * NP);
+  rc |= dalloc(b, ga.tag, (size_t)ncol * NP);
+  rc |= dalloc(b, ga.val, (size_t)ncol * NP);
+  rc |= dalloc(b, ca.tuple_action, (size_t)(NP * A));
+  rc |= batch_device_buffers(b, (size_t)3 * d.n_strings);
+  if (rc != 0) { cbh_batch_release(b); return -1; }
+  d.req_u32 = ga.req; d.col_tag = ga.tag; d.col_val = ga.val; d.tuple_action = ca.tuple_action;
+  if (d.n_strings && hipMemsetAsync(d.gbits, 0, (size_t)3 * d.n_strings * sizeof(u64), s) != hipSuccess) { cbh_batch_release(b); return fail("upload failed"); }
+  hipLaunchKernelGGL(cbh_cross_gather_kernel, dim3((n_pairs + 255u) / 256u), dim3(256), 0, s, ga);
+  hipLaunchKernelGGL(cbh_cross_actions_kernel, dim3((u32)(((NP * A + 3u) / 4u + 255u) / 256u)), dim3(256), 0, s, ca);
+  if (hipGetLastError() != hipSuccess) { cbh_batch_release(b); return fail("cbh_cross_pairs_upload: the gather failed to launch"); }
+  // (the pair lists are the caller's pageable memory: their copies must have left before the call returns - batch_compact synchronises, or the wait below)
+  if (batch_compact(b, s) != 0) { cbh_batch_release(b); return -1; }
+  if (hipStreamSynchronize(s) != hipSuccess) { cbh_batch_release(b); return fail("upload failed"); }
+  *out = b;
+  return 0;
+}
+extern "C" int cbh_cross_pairs_upload(cbh_table* t, cbh_cross_set* set, const uint32_t* pair_p, const uint32_t* pair_r, uint32_t n_pairs, cbh_device_batch** out) {
+  try { return cross_pairs_upload(t, set, pair_p, pair_r, n_pairs, out); } catch (...) { return fail("out of memory"); }
 }
 
 

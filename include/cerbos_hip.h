@@ -283,7 +283,7 @@ int cbh_kernel_time_ms(cbh_table* t, float* check_kernel_ms, float* resolve_kern
  * range, a device allocation that fails.
  * Not here: one product sharded over several devices (split the resources and call once per device);
  * cbh_check_batch_trail / cbh_trace_batch on a product (flatten the few inputs marked CBH_ST_CEL_ERROR / CBH_ST_WANTS_TRACE
- * explicitly and trace those).  Deciding straight from the halves without materialising the product: cbh_cross_upload, below. */
+ * explicitly and trace those).  Deciding straight from the halves without materialising the product: cbh_cross_upload_ex, below. */
 #define CBH_HAS_CROSS 1
 typedef struct cbh_cross {
   uint32_t n_principals, n_resources, n_actions; /* N, M, A */
@@ -311,14 +311,23 @@ int cbh_result_download_allow_bits(cbh_table* t, cbh_device_batch* b, uint64_t* 
  * planes of the same layout, bit set = the tuple's status is not CBH_ST_OK (a CEL error, CBH_ST_WANTS_TRACE) - the tuples to take
  * to another road for their full result; the library never hides a status behind a bit.
  *
- * cbh_cross_upload: `halves` and `x` as for cbh_batch_upload_cross; in addition the halves' own role and action slices must lie
+ * cbh_cross_upload_ex: `halves` and `x` as for cbh_batch_upload_cross; in addition the halves' own role and action slices must lie
  * inside the batch (every row is read when the compact form is derived).  Returns 0 and the set; < 0 on an error (what
- * cbh_batch_upload_cross refuses, except the bound on N * M); 1 = nothing was built because the set has no direct form - take
- * cbh_batch_upload_cross, which gives the same answers (cbh_last_error says why): a table that is not flat or has derived roles,
- * more than four actions, a principal with more than four roles, a row of the halves with more than four actions or a field
- * that does not fit the compact record, an attribute value that needs the evaluator (an int, uint, list or map in a column a
- * classified leaf compares: the `_any` kernels), a table with membership leaves or other conditions outside the classified
- * leaves that is decided by the mask walk (long buckets: cbh_check_flat_kernel_any_masks has no direct form).
+ * cbh_batch_upload_cross refuses, except the bound on N * M; a bit in `accept` that this library does not know); 1 = nothing was
+ * built because the set has no direct form - take cbh_batch_upload_cross, which gives the same answers (cbh_last_error says why).
+ * `accept` says which sets beyond the first version's the caller is prepared for (a caller written against cbh_cross_upload relies
+ * on 1 to route, and may have sized its planes for four actions):
+ *   CBH_CX_DERIVED_ROLES  a flat table with derived roles (cbh_check_flat_kernel_dr_x; its staged and mask plans take the ordinary
+ *                         `_x` kernels).  Derived-role conditions make flagged tuples common - a condition that reads an attribute
+ *                         some row lacks is a CEL error, reported under CBH_F_WANT_DERIVED_ROLES even where no rule needed the
+ *                         role: ask for `flagged`, and see cbh_cross_pairs_upload.
+ *   CBH_CX_ACTION_GROUPS  5 .. CBH_MAX_ACTIONS_PER_REQUEST actions, decided four at a time: (A + 3) / 4 launches of the same kernel per
+ *                         check, one download.  The planes stay [A][words_per_plane], action-major, for every A.
+ * Without its bit such a set returns 1, as every set without a direct form: a table that is not flat, a principal with more than
+ * four roles, a field of the halves that does not fit the compact record, an attribute value that needs the evaluator (an int, uint,
+ * list or map in a column a classified leaf compares: the `_any` kernels), a table with membership leaves or other conditions
+ * outside the classified leaves that is decided by the mask walk (long buckets: cbh_check_flat_kernel_any_masks has no direct form).
+ * cbh_cross_upload(t, i, halves, x, out) is cbh_cross_upload_ex(t, i, halves, x, 0, out).
  * A flat table decided by the record walks (MODE 0 / 1) whose conditions are classified leaves and membership in a list or map
  * the request brings gets the materialised road's answers bit for bit.  If such a table ALSO holds a condition that only the
  * evaluator call decides, the set is still served, loudly: the tuples whose answer needs that condition come back flagged
@@ -328,15 +337,31 @@ int cbh_result_download_allow_bits(cbh_table* t, cbh_device_batch* b, uint64_t* 
  * or more, words_per_plane < W, a failed allocation or copy - the set stays usable), nothing is written for a refused argument;
  * 1 = these flags choose a plan without a direct form (CBH_F_STRICT_EVALUATION, CBH_F_WANT_EFFECTIVE_POLICIES).
  * CBH_F_LENIENT_SCOPE_SEARCH is served.  Calls on one set queue in call order; the result words on the device are reused
- * from tile to tile.  cbh_cross_describe: the kernel a check with these flags would launch, or "none: ..." .
- * Not here: trails and the trace pass on a set; tables with derived roles; more than four actions; sharding over devices. */
+ * from tile to tile.  cbh_cross_describe: the kernel a check with these flags would launch (and ", G action groups" where it
+ * launches it more than once), or "none: ..." .
+ *
+ * The full answer of chosen pairs - the flagged ones: cbh_cross_pairs_upload builds, on the device and from the set's own rows, the
+ * resident batch of n_pairs requests x A actions in which request q pairs device principal pair_p[q] (< N) with device resource
+ * pair_r[q] (< M): the set's device orders, i.e. bit q of a tile's plane decodes to pair_r = r_begin + q / N, pair_p = q % N.
+ * Duplicates are allowed.  The batch is a resident batch like any other, with the shape a host-built batch of those requests
+ * would get: cbh_check_resident, cbh_result_download, cbh_batch_set_trail / cbh_trail_download, cbh_batch_release; it does not
+ * depend on the set afterwards.  < 0: a null argument, an index out of range (checked before anything is launched), n_pairs of 0,
+ * n_pairs * A of 2^32 or more, a set of another table, a failed allocation or copy.
+ * Not here: one set sharded over several devices (split the resources); trails and the trace pass directly on a set (take the
+ * pairs batch; cbh_trace_batch takes host batches only). */
 #define CBH_HAS_CROSS_DIRECT 1
+#define CBH_HAS_CROSS_DIRECT_EX 1
+#define CBH_CX_DERIVED_ROLES 1u   /* accept a flat table with derived roles */
+#define CBH_CX_ACTION_GROUPS 2u   /* accept 5 .. CBH_MAX_ACTIONS_PER_REQUEST actions, decided four at a time */
 typedef struct cbh_cross_set cbh_cross_set;
 int cbh_cross_upload(cbh_table* t, uint32_t device_index, const cbh_batch* halves, const cbh_cross* x, cbh_cross_set** out);
+int cbh_cross_upload_ex(cbh_table* t, uint32_t device_index, const cbh_batch* halves, const cbh_cross* x, uint32_t accept, cbh_cross_set** out);
 int cbh_cross_check(cbh_table* t, cbh_cross_set* set, const cbh_params* p, uint32_t r_begin, uint32_t r_end,
                     uint64_t* allow, uint64_t* flagged, size_t words_per_plane);
 const char* cbh_cross_describe(cbh_table* t, cbh_cross_set* set, const cbh_params* p);
 void cbh_cross_release(cbh_cross_set* set);
+int cbh_cross_pairs_upload(cbh_table* t, cbh_cross_set* set, const uint32_t* pair_p, const uint32_t* pair_r, uint32_t n_pairs,
+                           cbh_device_batch** out);
 
 /* ---- Device-side ingest: serialized CheckInputs in, a resident batch out (the GPU flattens) ----------------------
  * The reference decodes each CheckInput and builds its request view on the CPU (internal/ruletable/check.go:536-554); so did

@@ -11,7 +11,7 @@ wave's path: blocks that exclude each other (packed / wide tags, the fallbacks b
 tables, the per-lane loop that climbs to a scope with a policy) all show up; what to look for is a trip that carries bulk loads
 (lds-copy, the request words) behind an earlier one that did too.
 
-    python tools/audit_prologue_waits.py [kernel-name-substring ...]        (default: the flat kernel, its derived-role variant, the mask walk, their compact instantiations, the walk)
+    python tools/audit_prologue_waits.py [kernel-name-substring ...]        (default: the flat kernel, its derived-role variant, the mask walk, their compact instantiations, the derived-role direct cross kernel, the walk)
     python tools/audit_prologue_waits.py --lib path/to/libcerbos_hip.so ...
 
 Exit status 1 if a listed kernel's prologue has more than --max-bulk-trips (default 3) BULK trips - trips that carry asynchronous copies
@@ -29,7 +29,7 @@ LLVM = "/opt/rocm/lib/llvm/bin"
 
 ap = argparse.ArgumentParser()
 ap.add_argument("kernels", nargs="*", default=["cbh_check_flat_kernel10", "cbh_check_flat_kernel_dr10", "cbh_check_flat_kernel_masks10", "cbh_check_flat_kernel_c10",
-                                               "cbh_check_flat_kernel_masks_c10", "cbh_walk2_kernel10"])
+                                               "cbh_check_flat_kernel_masks_c10", "cbh_check_flat_kernel_dr_x10", "cbh_walk2_kernel10"])
 ap.add_argument("--lib", default=os.path.join(ROOT, "cerbos_amd", "libcerbos_hip.so"))
 ap.add_argument("--max-bulk-trips", type=int, default=3)
 args = ap.parse_args()

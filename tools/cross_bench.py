@@ -20,6 +20,17 @@ same, so it must not differ).
                                                    and cbh_compact_pack_kernel write, to be divided by the trace's kernel times
   python tools/cross_bench.py --profile-direct c2:4096:1024
                                                    ONE direct leg and nothing else, for a kernel trace
+  python tools/cross_bench.py --skip-host --configs c3:4096:1024,c2:4096:1024:16
+                                                   a configuration is NAME:N:M or NAME:N:M:A - C3 (derived roles) and more than four
+                                                   actions go direct through cbh_cross_upload_ex (every `accept` bit set); A > 4 takes
+                                                   the workload's further actions, then names no policy knows.  --skip-host: without
+                                                   the host leg (numpy lays out N * M * A on the host: minutes at 4096 x 1024 x 16)
+  python tools/cross_bench.py --check-alone c3:4096:1024
+                                                   the direct check alone (inputs resident, planes copied to the host), one line: for an
+                                                   A/B of two builds or switches (CBH_CROSS_DR_MEMO=0), one process per repetition
+  python tools/cross_bench.py --pairs c3:4096:1024:65536
+                                                   CrossSet.pairs_batch of that many random pairs, wall clock (under rocprofv3
+                                                   --kernel-trace --stats: the device time of cbh_cross_gather_kernel)
 One JSON line per configuration on stdout."""
 import argparse
 import json
@@ -73,10 +84,19 @@ def timed(table, reps, warmup, body):
     return out
 
 
-def setup(name, n, m):
+def parse(cfg):
+    """NAME:N:M[:A] -> (name, n, m, a or None)"""
+    f = cfg.split(":")
+    return f[0], int(f[1]), int(f[2]), (int(f[3]) if len(f) > 3 else None)
+
+
+def setup(name, n, m, a=None):
     lt = lower_rule_table(rule_table_from_policies(policies_from_docs(getattr(workloads, name + "_policies")())))
     ins = getattr(workloads, name + "_requests")(n + m, seed=17).to_inputs()
     principals, resources, actions = [i["principal"] for i in ins[:n]], [i["resource"] for i in ins[n:]], list(ins[0]["actions"])
+    if a is not None:     # the workload's own actions first, then its further ones, then names no policy knows
+        more = [x for x in getattr(workloads, name.upper() + "_ACTIONS", []) if x not in actions]
+        actions = (actions + more + ["unknown%02d" % i for i in range(64)])[:a]
     fl = Flattened(Flattener(lt))
     table = capi.Table(lt.blob)
     table.set_resident_streams(1)
@@ -104,7 +124,7 @@ def device_leg(lt, table, fl, p, r, a):
 
 def direct_leg(lt, table, fl, p, r, a):
     def body():
-        cs = cross.cross_direct_upload(table, fl, lt.columns, p, r, a)
+        cs = cross.cross_direct_upload(table, fl, lt.columns, p, r, a, accept=capi.CX_ALL)
         if cs is None:
             raise SystemExit("the set has no direct form")
         cs.check(0, len(r), now_ns=NOW)
@@ -137,10 +157,40 @@ def main():
     ap.add_argument("--configs", default="c2:1024:1024,c2:4096:1024,t:1024:1024,t:4096:1024")
     ap.add_argument("--profile", default=None, metavar="NAME:N:M")
     ap.add_argument("--profile-direct", default=None, metavar="NAME:N:M")
+    ap.add_argument("--skip-host", action="store_true")
+    ap.add_argument("--check-alone", default=None, metavar="NAME:N:M[:A]")
+    ap.add_argument("--pairs", default=None, metavar="NAME:N:M:COUNT")
     args = ap.parse_args()
     if args.reps < 10:
         ap.error("at least 10 timed repetitions")
     capi.init(0)
+    if args.check_alone:
+        name, n, m, na = parse(args.check_alone)
+        lt, table, fl, p, r, a = setup(name, n, m, na)
+        cs = direct_leg(lt, table, fl, p, r, a)()
+        t = timed(table, args.reps, args.warmup, lambda: cs.check(0, m, now_ns=NOW) and None)
+        print(json.dumps({"check_alone": args.check_alone, "kernel": cs.describe(), "a": len(a),
+                          "direct_check_alone": stats(t, n * m * len(a)), "median_ms": float(np.median(t)) * 1e3}), flush=True)
+        cs.close()
+        table.close()
+        return
+    if args.pairs:
+        name, n, m, cnt = parse(args.pairs)
+        lt, table, fl, p, r, a = setup(name, n, m)
+        cs = direct_leg(lt, table, fl, p, r, a)()
+        rng = np.random.default_rng(5)
+        pp, pr = rng.integers(0, n, size=cnt).astype(np.uint32), rng.integers(0, m, size=cnt).astype(np.uint32)
+        t = timed(table, args.reps, args.warmup, lambda: cs.pairs_batch(pp, pr))
+        db = cs.pairs_batch(pp, pr)
+        t2 = launch_alone(table, db, args.reps, args.warmup)
+        print(json.dumps({"pairs": args.pairs, "columns": len(lt.columns), "plan": table.plan(db),
+                          "pairs_batch_ms": {"min": min(t) * 1e3, "median": float(np.median(t)) * 1e3, "max": max(t) * 1e3},
+                          "launch_alone": stats(t2, cnt * len(a)),
+                          "cbh_cross_gather_kernel_bytes_written": cnt * (64 + 9 * len(lt.columns))}), flush=True)
+        db.close()
+        cs.close()
+        table.close()
+        return
     if args.profile_direct:
         name, n, m = args.profile_direct.split(":")
         n, m = int(n), int(m)
@@ -168,22 +218,22 @@ def main():
         table.close()
         return
     for cfg in args.configs.split(","):
-        name, n, m = cfg.split(":")
-        n, m = int(n), int(m)
-        lt, table, fl, p, r, a = setup(name, n, m)
+        name, n, m, na = parse(cfg)
+        lt, table, fl, p, r, a = setup(name, n, m, na)
         decisions = n * m * len(a)
         line = {"workload": name, "n": n, "m": m, "a": len(a), "decisions": decisions, "columns": len(lt.columns),
                 "unit": "decisions per second, end to end (min / median / max over the timed repetitions)"}
-        line["host_leg"] = stats(timed(table, args.reps, args.warmup, host_leg(lt, table, fl, p, r, a)), decisions)
-        hb = table.upload(cross.cross_product_batch(fl, lt.columns, p, r, a))
-        line["host_batch_plan"] = table.plan(hb)
-        line["host_batch_launch_alone"] = stats(launch_alone(table, hb, args.reps, args.warmup), decisions)
-        hb.close()
+        if not args.skip_host:
+            line["host_leg"] = stats(timed(table, args.reps, args.warmup, host_leg(lt, table, fl, p, r, a)), decisions)
+            hb = table.upload(cross.cross_product_batch(fl, lt.columns, p, r, a))
+            line["host_batch_plan"] = table.plan(hb)
+            line["host_batch_launch_alone"] = stats(launch_alone(table, hb, args.reps, args.warmup), decisions)
+            hb.close()
         if not args.host_only:
             dev_t, dir_t = timed_alternating(table, args.reps, args.warmup, [device_leg(lt, table, fl, p, r, a), direct_leg(lt, table, fl, p, r, a)])
             line["device_leg"] = stats(dev_t, decisions)
             line["direct_leg"] = stats(dir_t, decisions)
-            cs = cross.cross_direct_upload(table, fl, lt.columns, p, r, a)
+            cs = cross.cross_direct_upload(table, fl, lt.columns, p, r, a, accept=capi.CX_ALL)
             line["direct_kernel"] = cs.describe()
 
             def check_alone():
@@ -194,7 +244,8 @@ def main():
             line["device_batch_plan"] = table.plan(db)
             line["device_batch_launch_alone"] = stats(launch_alone(table, db, args.reps, args.warmup), decisions)
             db.close()
-            line["device_slowest_over_host_fastest"] = line["device_leg"]["min"] / line["host_leg"]["max"]
+            if not args.skip_host:
+                line["device_slowest_over_host_fastest"] = line["device_leg"]["min"] / line["host_leg"]["max"]
         table.close()
         print(json.dumps(line), flush=True)
 

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """hipcc -Rpass-analysis=kernel-resource-usage remarks (stderr of a build) -> one line per kernel.
-usage: hipcc ... -Rpass-analysis=kernel-resource-usage 2> res.txt; python tools/kernel_resources.py res.txt [filter]"""
+usage: hipcc ... -Rpass-analysis=kernel-resource-usage 2> res.txt; python tools/kernel_resources.py res.txt [filter]
+(filter: a substring of the kernels' names - `_x` for the direct cross instantiations, cbh_check_flat_kernel_dr_x among them, `cbh_cross_` for
+the cross road's small kernels)"""
 import re
 import sys
 
