@@ -22,6 +22,7 @@ F_WANT_DERIVED_ROLES = 4
 F_WANT_EFFECTIVE_POLICIES = 8
 CX_DERIVED_ROLES, CX_ACTION_GROUPS = 1, 2        # cbh_cross_upload_ex `accept`
 CX_ALL = CX_DERIVED_ROLES | CX_ACTION_GROUPS
+CX_ROLE_GROUPS = 16                               # ... principals with 5 .. 16 roles (not in CX_ALL: 4 and 8 stay unknown bits)
 
 EFFECT_ALLOW, EFFECT_DENY = 1, 2
 ST_OK, ST_CEL_ERROR, ST_UNSUPPORTED, ST_WANTS_TRACE = 0, 1, 2, 3
@@ -453,7 +454,8 @@ class Table:
         ``n_principals`` + ``n_resources`` rows and ``CrossSet.check`` decides tiles of resources straight from them.  Returns the
         ``CrossSet``, or None where the set has no direct form (return value 1: take ``upload_cross``, which gives the same answers).
         ``accept``: ``CX_DERIVED_ROLES`` | ``CX_ACTION_GROUPS`` (``CX_ALL``) - the sets beyond ``cbh_cross_upload``'s the caller is
-        prepared for; 0 is ``cbh_cross_upload`` itself."""
+        prepared for; 0 is ``cbh_cross_upload`` itself.  ``CX_ROLE_GROUPS`` (beside ``CX_ALL``): principals with five to
+        sixteen roles, decided four roles at a time - ``CrossSet.describe`` then ends in ", R role groups]"."""
         cb = make_cbatch(halves_batch, self.num_columns)
         act = np.ascontiguousarray(action_ids, dtype=np.uint32)
         po = None if p_order is None else np.ascontiguousarray(p_order, dtype=np.uint32)

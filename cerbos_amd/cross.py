@@ -121,13 +121,16 @@ def cross_direct_upload(table, flattener, columns, principals, resources, action
     ``capi.CrossSet.check`` decides tiles of resources straight from them - N * M is bounded by what the caller wants back, not by
     device memory.  Returns the ``capi.CrossSet`` with ``shape``, ``p_order``, ``r_order`` (``allow_cube_planes`` accepts it), or
     None where the set has no direct form: take ``cross_product_upload``, which gives the same answers.  ``accept``:
-    ``capi.CX_DERIVED_ROLES`` | ``capi.CX_ACTION_GROUPS`` - tables with derived roles, more than four actions; by default neither."""
+    ``capi.CX_DERIVED_ROLES`` | ``capi.CX_ACTION_GROUPS`` | ``capi.CX_ROLE_GROUPS`` - tables with derived roles, more than four
+    actions, principals with five to sixteen roles (decided four roles at a time; ``sort=True`` orders the principals by role
+    count, which keeps the wide ones together in a wave); by default none."""
     h, p_order, r_order, act_ids = cross_halves(flattener, principals, resources, actions, aux_data, default_policy_version, default_scope, sort)
     return direct_upload_halves(table, h, len(principals), len(resources), act_ids, p_order, r_order, device_index, accept)
 
 
 def direct_upload_halves(table, halves, n, m, act_ids, p_order, r_order, device_index=0, accept=0):
-    """``cross_direct_upload`` for halves that are flattened already; an order of None is the identity."""
+    """``cross_direct_upload`` for halves that are flattened already; an order of None is the identity.  ``accept`` as there
+    (``capi.CX_ROLE_GROUPS``: the halves may hold principals with up to sixteen roles)."""
     cs = table.cross_upload(halves, n, m, act_ids, p_order, r_order, device_index=device_index, accept=accept)
     if cs is not None:
         cs.p_order = np.arange(n) if p_order is None else np.asarray(p_order)

@@ -448,6 +448,12 @@ __device__ __forceinline__ u64 load_u64g(const CBH_G u32* p) {   // 8-byte align
 // principal's record, kind, version and scope from the resource's, the actions from the launch (the same for every lane), the
 // columns from either row by their side (cc_fill_cross).  The walk and the fold are the same; no result word is written - one
 // ballot per action (and one of "status is not OK", where wanted) is stored by the wave's first lane.
+// A set whose principals have five to sixteen roles is decided four roles at a time (CrossRoleGroup.role_group, cbh_host_resident.h
+// cross_set_check): the launch of group g >= 1 takes the lanes' roles from the group's role words, leaves out the walks of the actions
+// an earlier group allowed and ORs its ballots into the planes.  For the two bits this is the reference's role loop unrolled: an
+// action is allowed iff some role allows it; an evaluation counts iff no earlier role allowed the action - within a group the fold's
+// `seen`, across groups the earlier groups' allow bit; the scopes whose definitions are evaluated are the union of the scopes the
+// groups' legitimate walks reach (with ALL of the principal's roles against the parent roles: CrossRoleGroup.rc_all).
 // CROSS with MEMO (cbh_check_flat_kernel_dr_x, a table with derived roles): the memo needs nothing of its own here.  A reference is
 // wave-uniform as before (a record's, a scope's definition's); on a miss the outcome is computed for EVERY lane - each lane has its
 // pair's two rows in its slice of the column cache, and a lane beyond the tile's end shadows pair 0 with no role and no action, so
@@ -487,6 +493,7 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c, con
   u32 cls_a0 = 0, cls_r0 = 0;
   bool spec = false; u32 spec_ix = 0;
   u32 x_prow = 0, x_rrow = 0;   // CROSS: the lane's two rows of the halves
+  u32 x_done = 0;               // CROSS, role group >= 1: bit k = an earlier group's role allowed action k
   if constexpr (CROSS) {
     // ---- the pair (cbh_cross.h: resource-major, q = j' * N + i').  A lane beyond the tile's end shadows q = 0 with no action and no role.
     const u32 jp = req / x.n, ip = req - jp * x.n;
@@ -502,6 +509,23 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c, con
 #pragma unroll
     for (u32 k = 0; k < 4; ++k) rc[k] = valid ? rc[k] : 31u;
     act_off = 0;
+    if (x.rg && x.rg->role_group) {   // uniform
+      // ---- a further group of four roles (cerbos_hip.h CBH_CX_ROLE_GROUPS): the roles 4 g .. 4 g + 3 of the principal come from the
+      // group's role word, and what the earlier groups' launches decided from the planes they wrote - a plane word is exactly this
+      // wave's ballot in every launch, so each lane reads its own bit.  An action an earlier role allowed is decided (check.go:429-442:
+      // the first role that allows): its walks in this group are not evaluations the reference makes, they are not walked at all.
+      // A wave without a walk left returns before any other work: it would store what the planes already hold.
+      const u32 rw = x.rg->role_words[x_prow];
+      const u32 xa = (x.act_word >> 20) & 7u, word = w0r >> 6;
+      u32 prev = 0;
+#pragma unroll
+      for (u32 k = 0; k < 4; ++k) if (k < xa && w0r < x.n_tile) prev |= ((u32)(x.allow[(size_t)k * x.words + word] >> c.tid) & 1u) << k;
+      role_cnt = valid ? (rw >> 20) & 7u : 0u;
+#pragma unroll
+      for (u32 k = 0; k < 4; ++k) rc[k] = valid ? (rw >> (5u * k)) & 31u : 31u;
+      x_done = prev;
+      if (wave_ballot(role_cnt != 0 && (((1u << act_cnt) - 1u) & ~prev) != 0) == 0) return;
+    }
   } else if constexpr (COMPACT) {
     // ---- the compact form (cbh_vm.h BatchDev.creq): ONE 16-byte load brings everything the walk takes from the request words, the
     // role ids and the action ids - the classes were looked up when the batch was uploaded.  First trip: the record; second:
@@ -541,7 +565,7 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c, con
   CcTags cct;
   if constexpr (COMPACT) { for (u32 g = 0; g < CBH_CACHE_COLS / 4; ++g) cct.w[g] = 0; } else cct = cc_load_tags(c, b, NR, w0, wd);   // (compact: the tags arrive as copies, cc_fill_compact)
   const bool ptags = COMPACT || (c.flags & CBH_FI_PACKED_TAGS) != 0;   // the form of the cache's tags (CBH_CC_DWORDS)
-  const u32 all = (1u << act_cnt) - 1u;
+  const u32 all = CROSS ? ((1u << act_cnt) - 1u) & ~x_done : (1u << act_cnt) - 1u;   // (CROSS: without the actions an earlier role group allowed)
   // [depth][lane]: scope index at that depth of the lane's chain - in the dynamic LDS behind the column caches,
   // sized by the table's longest chain (a one-scope table pays 256 B per wave, not 4 KB: LDS sets the occupancy here)
   const u32 max_depth = t.max_depth < CBH_FLAT_MAX_DEPTH ? t.max_depth : CBH_FLAT_MAX_DEPTH;
@@ -1099,6 +1123,11 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c, con
       reach = d + 1u;
     }
     bool derr = false, dr_unsup = false;
+    // (CROSS, a set with role groups: ALL of the principal's roles, not the launch's four - a definition whose parent role sits in
+    // another group is evaluated at the scopes this group's walks reach.  Loaded here: the path is rare.  And the errors are kept by
+    // chain position - bit d2 a CEL error, bit 16 + d2 outside the device subset - for what follows the climb)
+    u32 dr_rc = lane_rc, dmask = 0;
+    if constexpr (CROSS) { if (x.rg) dr_rc = x.rg->rc_all[x_prow]; }
     u32 cur2 = first, d2 = 0;   // the same merged climb as the walk above, for the scopes a legitimate walk reached
     for (;;) {
       const bool active = cur2 != CBH_NONE && d2 < reach;
@@ -1111,15 +1140,50 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c, con
       if (udir_find(t, BTYPE, g_ver, g_k, g_si, bucket)) {
         for (u32 d = bucket.z; d < bucket.z + bucket.w; ++d) {
           const TblDrx dx = uload_rec<TblDrx>(t.drx, d);
-          const bool applies = ing && (dx.rm_lo & lane_rc) != 0;   // parent roles x the request's roles (check.go:244)
+          const bool applies = ing && (dx.rm_lo & dr_rc) != 0;   // parent roles x the request's roles (check.go:244)
           if (wave_ballot(applies) == 0) continue;
           u32 lv = 1u;
           if (dx.cond != CBH_NONE) lv = leafish_memo(dx.cond, dx.flags & 3u, [&] { return dx.leaf; }, applies);
+          if constexpr (CROSS) { if (applies) dmask |= (((lv & 2u) >> 1) | ((lv & 8u) << 13)) << d2; } else
           if (applies) { if (lv & 1u) edr |= 1ull << dx.name; derr = derr || (lv & 2u) != 0; dr_unsup = dr_unsup || (lv & 8u) != 0; }
         }
       }
       const u32 up = uchain_next(t, uload(&t.scope_parent[g_si]), FLAG_RES);
       if (ing) { cur2 = up; ++d2; }
+    }
+    if constexpr (CROSS) {
+      derr = (dmask & 0xFFFFu) != 0; dr_unsup = (dmask >> 16) != 0;
+      // Where such an error is marked.  Here and in the walk's kernels it is a per-request fact, marked on every action; the
+      // general walk, which decides the requests of the materialised product that no shape of the walk holds, marks the actions a
+      // legitimate walk was still going for when it reached the definition's scope.  The planes are the product's status, so a
+      // principal of that many roles (CrossRoleGroup.open_from: the host knows the product's plan) gets the general walk's marks:
+      // action k where an error lies below the deepest position a legitimate walk of k reached.
+      if (x.rg) {
+        if (dmask != 0 && x.rg->p_role_cnt[x_prow] >= x.rg->open_from) {
+          u32 e1 = 0, u1 = 0;
+#pragma unroll
+          for (u32 k = 0; k < 4; ++k) {
+            const u32 lk = legit & (0x1111u << k);
+            u32 below = 0;   // the chain positions a legitimate walk of action k reached, as a mask
+            if (lk & ~done) below = 0xFFFFu;
+            else if (lk) {
+              u32 cand = lk, d = 0;
+              u32 tp = cand & dp3; if (tp) { cand = tp; d |= 8u; }
+              tp = cand & dp2; if (tp) { cand = tp; d |= 4u; }
+              tp = cand & dp1; if (tp) { cand = tp; d |= 2u; }
+              tp = cand & dp0; if (tp) { cand = tp; d |= 1u; }
+              below = (2u << d) - 1u;
+            }
+            e1 |= (dmask & below) ? 1u << (8u * k) : 0u;
+            u1 |= ((dmask >> 16) & below) ? 1u << (8u * k) : 0u;
+          }
+          const u32 un = (st4 >> 1) & ~st4 & 0x01010101u;   // bytes that read 2
+          const u32 em = (e1 & ~un) * 0xFFu, um = u1 * 0xFFu;
+          st4 = (st4 & ~em) | (em & 0x01010101u);
+          st4 = (st4 & ~um) | (um & 0x02020202u);
+          derr = false; dr_unsup = false;
+        }
+      }
     }
     if (derr) {   // evaluation errors are a per-request fact: every action that is not UNSUPPORTED
       const u32 un = (st4 >> 1) & ~st4 & 0x01010101u;   // bytes that read 2
@@ -1138,8 +1202,13 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c, con
       const u64 ma = wave_ballot(in && alw[k]);
       const u64 mf = wave_ballot(in && ((st4 >> (8u * k)) & 0xFFu) != (u32)CBH_ST_OK);
       if (c.tid == 0 && k < xa && w0r < x.n_tile) {
-        x.allow[(size_t)k * x.words + word] = ma;
-        if (x.flagged) x.flagged[(size_t)k * x.words + word] = mf;
+        if (x.rg && x.rg->role_group) {   // (group 0 stores unconditionally: the device words are reused from tile to tile, a stale one is never read)
+          x.allow[(size_t)k * x.words + word] |= ma;
+          if (x.flagged) x.flagged[(size_t)k * x.words + word] |= mf;
+        } else {
+          x.allow[(size_t)k * x.words + word] = ma;
+          if (x.flagged) x.flagged[(size_t)k * x.words + word] = mf;
+        }
       }
     }
     return;
@@ -1356,7 +1425,8 @@ static inline bool cbh_is_flat_compact_kernel(cbh_check_kernel_fn fn) {
 }
 // The direct cross road's instantiations (flat_body CROSS; cerbos_hip.h cbh_cross_check): MODE 0, 1, 2 without the evaluator call, the
 // cross arguments a by-value parameter of their own.  Same attributes as their compact siblings.  A set of more than four actions is
-// decided by several launches of the same kernel, four actions each (cbh_host_resident.h cross_set_check): nothing here knows.
+// decided by several launches of the same kernel, four actions each (cbh_host_resident.h cross_set_check): nothing here knows.  So is a
+// set of principals with more than four roles, four roles each: CrossRoleGroup.role_group.
 __global__ CBH_FLAT_ATTRS(7) void cbh_check_flat_kernel_x(const KernelArgs a, const KernelArgs* __restrict__ ka, const CrossDev x) {
   CBH_FLAT_CTX_C(a, ka);
   flat_body<false, 0, false, false, true, true>(a, c, x);

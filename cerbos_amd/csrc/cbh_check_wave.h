@@ -522,12 +522,22 @@ __device__ __forceinline__ void cc_fill_compact(const Ctx& c, const BatchDev& b,
 // kernel parameter of their own - KernelArgs, BatchDev and OutDev keep their layout.  The batch of the launch is the HALVES batch
 // in its compact form (N principals' rows, then M resources'); request q of the tile pairs principal p_order[q % n] with resource
 // r_order[r_begin + q / n].
+// One launch of a set with role groups, in device memory (one record per group, written at upload): behind ONE pointer, because
+// every further kernel argument is a scalar register the whole kernel holds.
+struct CrossRoleGroup {
+  const CBH_G u32* role_words;   // group >= 1: [halves row of the principal] the classes and the count of its roles 4 g .. 4 g + 3, in act_word's format
+  const CBH_G u32* rc_all;       // [halves row of the principal] OR of 1 << class over ALL its roles
+  const CBH_G u32* p_role_cnt;   // [halves row of the principal] its true role count
+  u32 role_group;                // g: which four roles of the principals this launch decides
+  u32 open_from;                 // a principal of at least this many roles: the general walk's marks for a derived-role error (flat_body)
+};
 struct CrossDev {
   const CBH_G u32* p_order; const CBH_G u32* r_order;   // [n], [m], or null = identity
   CBH_G u64* allow; CBH_G u64* flagged;                 // [actions][words] ballots, action-major; flagged: null = not wanted
   u32 n, r_begin, n_tile, words;                        // principals; first resource of the tile; its requests n * (r_end - r_begin); (n_tile + 63) / 64
   u32 side;                                             // bit k = cached column k travels with the resource (CrossArgs.col_side)
   u32 act_word;                                         // action classes 0..3 (5 bits each, as in word 3 of a compact record) | action count << 20
+  const CBH_G struct CrossRoleGroup* rg;                // a set with role groups (cerbos_hip.h CBH_CX_ROLE_GROUPS): this launch's group; null = a set without them
 };
 // cc_fill_compact for a lane whose request is a PAIR of rows of the halves' compact form: column k's copies read at the resource's
 // row where bit k of `side` (wave-uniform) is set, at the principal's otherwise - lds_dma_dword takes a per-lane address.  The tags:

@@ -3,7 +3,7 @@
 // resident batch the decision kernels read unchanged.  And the two kernels of the DIRECT road (cbh_cross_upload_ex) - the one lane that
 // writes the action words, and the gather that turns chosen pairs of a set into a resident batch (cbh_cross_pairs_upload) -, which
 // materialises no product: its decision kernels are the flat kernels' CROSS instantiations (cbh_check_flat.h), which read the
-// halves' compact form in place and write ballots.
+// halves' compact form in place and write ballots.  And the lane per principal that writes a wide set's role words.
 //
 // The product's layout: N principals x M resources, resource-major.  Device request q = j' * N + i' pairs the
 // j'-th resource with the i'-th principal of the caller's orders; the halves batch holds the N principals in its first N
@@ -102,6 +102,40 @@ __global__ __launch_bounds__(64) void cbh_cross_act_word_kernel(CrossActWordArgs
   }
 }
 
+// The direct road's role words (CrossRoleGroup.role_words / rc_all) of a set whose principals have up to CBH_CX_MAX_ROLES roles (cerbos_hip.h
+// CBH_CX_ROLE_GROUPS): the compact record of a principal holds its first four roles - group 0 - and per further group g the word
+// words[(g - 1) * n + row] holds the classes of its roles 4 g .. 4 g + 3 and their count, in the action words' format; all[row] is
+// the OR of 1 << class over ALL of its roles.  The classes by cbh_compact_pack_kernel's rule.  `role_off` is the halves' own request
+// word, `role_cnt` the principals' TRUE counts (the uploaded request words hold them clamped to four).  One lane per principal's
+// row, once per upload; the host has checked every slice against n_roles.
+struct CrossRoleWordArgs {
+  const CBH_G u32* role_off; const CBH_G u32* role_cnt; const CBH_G u32* roles; const CBH_G u8* role_class;
+  CBH_G u32* words; CBH_G u32* all;
+  u32 n, groups, K, pad;
+};
+__global__ __launch_bounds__(256) void cbh_cross_role_word_kernel(CrossRoleWordArgs x) {
+  const u64 r64 = (u64)blockIdx.x * 256u + threadIdx.x;
+  if (r64 >= x.n) return;
+  const u32 r = (u32)r64;
+  const u32 kmax = x.K ? x.K - 1u : 0u;
+  const u32 off = x.role_off[r], total = x.role_cnt[r];
+  u32 all = 0, w = 0;
+  for (u32 i = 0; i < 4u * x.groups; ++i) {
+    const u32 g = i >> 2, k = i & 3u;
+    if (k == 0) w = (total > 4u * g ? (total - 4u * g < 4u ? total - 4u * g : 4u) : 0u) << 20;
+    u32 cls = 31u;
+    if (i < total) {
+      const u32 rid = x.roles[off + i];
+      const u32 cr = x.K ? x.role_class[rid < x.K ? rid : kmax] : 31u;
+      cls = (rid < x.K && cr < 31u) ? cr : 31u;
+      all |= 1u << cls;
+    }
+    w |= cls << (5u * k);
+    if (k == 3u && g >= 1u) x.words[(size_t)(g - 1u) * x.n + r] = w;
+  }
+  x.all[r] = all;
+}
+
 // Chosen pairs of a direct set as an ordinary resident batch (cerbos_hip.h cbh_cross_pairs_upload): cbh_cross_expand_kernel for a LIST of
 // pairs.  Request q pairs device principal pair_p[q] with device resource pair_r[q] - the set's own orders, what a tile's bit index
 // decodes to - instead of dividing q; the host has checked every index against n and m before the launch.  One lane per pair; the
@@ -114,6 +148,7 @@ struct CrossGatherArgs {
   const CBH_G u32* pair_p; const CBH_G u32* pair_r;                        // [n_pairs] device indices, < n and < nh - n
   CBH_G u32* req; CBH_G u8* tag; CBH_G u64* val;                           // the batch: [CBH_RQ_NFIELDS][n_pairs], [n_columns][n_pairs] twice
   u32 n, nh, n_pairs, a, n_columns, pad;
+  const CBH_G u32* p_role_cnt;                                             // [n] the principals' true role counts by halves row, or null = the request words' (a set with role groups uploads those clamped)
 };
 __global__ __launch_bounds__(256) void cbh_cross_gather_kernel(CrossGatherArgs x) {
   const u64 q64 = (u64)blockIdx.x * 256u + threadIdx.x;
@@ -128,6 +163,7 @@ __global__ __launch_bounds__(256) void cbh_cross_gather_kernel(CrossGatherArgs x
     u32 v;
     if (f == CBH_RQ_ACT_OFF) v = q * x.a;
     else if (f == CBH_RQ_ACT_CNT) v = x.a;
+    else if (f == CBH_RQ_ROLE_CNT && x.p_role_cnt) v = x.p_role_cnt[pi];
     else v = x.h_req[f * NH + (((CBH_CROSS_R_FIELDS >> f) & 1u) ? ri : pi)];
     x.req[f * NP + q] = v;
   }

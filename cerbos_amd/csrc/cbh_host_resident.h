@@ -201,7 +201,8 @@ extern "C" int cbh_batch_upload(cbh_table* t, const cbh_batch* in, cbh_device_ba
 // host-built batch of the same requests gets (validate_batch's answers for that batch, without the batch).
 // (`bounded`: the product is materialised, so N * M and N * M * A must stay below 2^32 - the direct road, cbh_cross_upload, has no such bound)
 // (`plan_a`, set by the caller: the action count the plan is made for where it is not A - the direct road decides A > 4 four at a time)
-struct CrossShape { std::vector<u8> side; u32 maxr = 0, wide_lo = 0, wide_hi = 0; bool plain = true; u32 plan_a = 0; };
+// (`group_roles`, set by the caller: the plan is made for at most four roles - the direct road decides more four at a time)
+struct CrossShape { std::vector<u8> side; u32 maxr = 0, wide_lo = 0, wide_hi = 0; bool plain = true; u32 plan_a = 0; bool group_roles = false; };
 static int cross_validate(cbh_table* t, uint32_t device_index, const cbh_batch* h, const cbh_cross* x, bool bounded, CrossShape& cs) {
   if (device_index >= t->reps.size()) return fail("device index out of range");
   const u64 N = x->n_principals, M = x->n_resources, A = x->n_actions;
@@ -246,7 +247,7 @@ static int cross_validate(cbh_table* t, uint32_t device_index, const cbh_batch* 
   bool plain = true;
   {
     const u32 mf = t->meta[CBH_M_FLAGS];
-    const bool matters = ((mf & CBH_MF_FLAT) && (cs.plan_a ? cs.plan_a : A) <= 4 && maxr <= 4) || ((mf & CBH_MF_WALK2) && t->meta[CBH_M_GSLOTS_ALL] > t->meta[CBH_M_GSLOTS_GENERIC]);
+    const bool matters = ((mf & CBH_MF_FLAT) && (cs.plan_a ? cs.plan_a : A) <= 4 && (maxr <= 4 || cs.group_roles)) || ((mf & CBH_MF_WALK2) && t->meta[CBH_M_GSLOTS_ALL] > t->meta[CBH_M_GSLOTS_GENERIC]);
     u32 sens = t->meta[CBH_M_SENS_COLS];
     if (ncol < 32) sens &= (1u << ncol) - 1u;
     bool hit = false;
@@ -641,6 +642,10 @@ extern "C" int cbh_result_download_allow_bits(cbh_table* t, cbh_device_batch* b,
 // the principals' roles, plain tags) with the compact launch's LDS, over the tile's N * (r_end - r_begin) pairs - once per group
 // of four actions, on the set's stream, each launch writing its own planes; what comes back is one ballot word per 64 pairs and
 // action.  The planes' device words belong to the set's batch (the replica's pool) and serve every tile that fits them.
+// A set whose principals have five to CBH_CX_MAX_ROLES roles (CBH_CX_ROLE_GROUPS) is uploaded with the principals' role counts
+// clamped to four - the compact record then holds a principal's first four roles, group 0 - and keeps one role word per principal
+// and further group of four roles (cbh_cross_role_word_kernel); a check launches, per group of actions, role group 0, then 1, 2, ...
+// of the same kernel, each ORing into the planes what the groups before it left open (flat_body CROSS).
 struct cbh_cross_set {
   cbh_device_batch* b = nullptr;
   u32 n = 0, m = 0, a = 0, maxr = 0; bool plain = true;
@@ -652,19 +657,37 @@ struct cbh_cross_set {
   // principals' role counts by device position (the shape of a batch of chosen pairs), the length of the strings' bytes
   const u8* d_side = nullptr; const u32* d_act = nullptr;
   std::vector<u8> p_roles; u32 str_bytes_len = 0;
+  // a set with role groups (maxr > 4): [(groups - 1)][n] role words and [n] class masks of all roles, by halves row (CrossRoleGroup), and the
+  // principals' true role counts by halves row for the gather (the halves' request words on the device hold them clamped)
+  const u32* role_words = nullptr; const u32* rc_all = nullptr; const u32* d_role_cnt = nullptr;
+  const CrossRoleGroup* d_rg = nullptr;   // ... and the launches' records, one per role group (CrossDev.rg)
 };
 static u32 cross_groups(const cbh_cross_set* cs) { return (cs->a + 3u) / 4u; }
+static u32 cross_role_groups(const cbh_cross_set* cs) { return cs->maxr > 4u ? (cs->maxr + 3u) / 4u : 1u; }
+// The flagged planes are the status of the materialised product, and the kernels that decide a product of wide requests do not agree
+// on where an error of a derived-role definition is marked (cbh_check_flat.h flat_body): from how many roles on a principal's
+// requests would be decided by the general walk, by the product's own plan (launch_plan: CBH_FI_ONLY_WIDE / CBH_FI_ONLY_WIDER).
+// (The flags that change a product's plan - strict evaluation, the trail - have no direct form: the plan under flags 0 is the one.)
+static u32 cross_open_from(const TableDev& dev, const cbh_cross_set* cs) {
+  const CbhPlan pp = plan_for(dev, cs->a, cs->maxr, cs->plain, 0);
+  if (pp.kind == 0) return 0u;
+  if (pp.kind != 2 || !pp.wide_kernel) return 0xFFFFFFFFu;
+  if (pp.walk_wide || pp.walk_awide) return cs->a > CBH_W2_AWIDE_NA ? 0u : cs->a > CBH_W2_NA ? CBH_W2_NR + 1u : CBH_W2_WIDE_NR + 1u;   // cbh_is_wider
+  return cs->a > CBH_W2_NA ? 0u : CBH_W2_NR + 1u;                                                                                          // cbh_is_wide
+}
 static cbh_cross_kernel_fn cross_kernel_for(const cbh_cross_set* cs, u32 eval_flags, CbhPlan& pl) {
-  pl = plan_for(cs->b->rep->dev, std::min(cs->a, 4u), cs->maxr, cs->plain, eval_flags & ~(u32)CBH_FI_MASK);
+  // (for at most four roles: with more, plan_for picks a walk kernel, which has no `_x` variant)
+  pl = plan_for(cs->b->rep->dev, std::min(cs->a, 4u), std::min(cs->maxr, 4u), cs->plain, eval_flags & ~(u32)CBH_FI_MASK);
   if (pl.kind != 1 || (eval_flags & CBH_F_DEBUG_CYCLES)) return nullptr;
   return cbh_flat_cross_variant(pl.kernel);
 }
 static int cross_set_upload(cbh_table* t, uint32_t device_index, const cbh_batch* h, const cbh_cross* x, uint32_t accept, cbh_cross_set** out) {
   if (out) *out = nullptr;
   if (!t || !h || !x || !out) return fail("null argument");
-  if (accept & ~(uint32_t)(CBH_CX_DERIVED_ROLES | CBH_CX_ACTION_GROUPS)) return fail("cbh_cross_upload_ex: `accept` has a bit this library does not know");
+  if (accept & ~(uint32_t)(CBH_CX_DERIVED_ROLES | CBH_CX_ACTION_GROUPS | CBH_CX_ROLE_GROUPS)) return fail("cbh_cross_upload_ex: `accept` has a bit this library does not know");
   CrossShape shape;
   shape.plan_a = std::min(x->n_actions, 4u);
+  shape.group_roles = (accept & CBH_CX_ROLE_GROUPS) != 0;
   if (cross_validate(t, device_index, h, x, false, shape) != 0) return -1;
   Replica* rep = t->reps[device_index];
   const u32 N = x->n_principals, M = x->n_resources, A = x->n_actions;
@@ -672,11 +695,12 @@ static int cross_set_upload(cbh_table* t, uint32_t device_index, const cbh_batch
   if (!(rep->dev.flags & CBH_MF_FLAT)) { g_err = "cbh_cross_upload: no direct form - the table is not flat"; return 1; }
   if (rep->dev.n_dr && !(accept & CBH_CX_DERIVED_ROLES)) { g_err = "cbh_cross_upload: no direct form - the table has derived roles"; return 1; }
   if (A > 4 && !(accept & CBH_CX_ACTION_GROUPS)) { g_err = "cbh_cross_upload: no direct form - more than four actions"; return 1; }
-  if (shape.maxr > 4) { g_err = "cbh_cross_upload: no direct form - a principal has more than four roles"; return 1; }
+  if (shape.maxr > 4 && !(accept & CBH_CX_ROLE_GROUPS)) { g_err = "cbh_cross_upload: no direct form - a principal has more than four roles"; return 1; }
+  if (shape.maxr > CBH_CX_MAX_ROLES) { g_err = "cbh_cross_upload: no direct form - a principal has more than CBH_CX_MAX_ROLES (16) roles"; return 1; }
   if (!shape.plain) { g_err = "cbh_cross_upload: no direct form - an attribute value needs the evaluator (int / uint / list / map in a sensitive column)"; return 1; }
   if (!compact_inputs_on()) { g_err = "cbh_cross_upload: no direct form - compact inputs are switched off"; return 1; }
   {   // the kernel the product would be planned (mask walk of a table that is not closed over the classified leaves: cbh_flat_cross_mode)
-    const CbhPlan pl = plan_for(rep->dev, shape.plan_a, shape.maxr, shape.plain, 0);
+    const CbhPlan pl = plan_for(rep->dev, shape.plan_a, std::min(shape.maxr, 4u), shape.plain, 0);
     if (pl.kind != 1 || !cbh_flat_cross_variant(pl.kernel)) { g_err = "cbh_cross_upload: no direct form - the kernel planned for this table has no direct instantiation"; return 1; }
   }
   cbh_cross_set* cs = new (std::nothrow) cbh_cross_set();
@@ -685,14 +709,21 @@ static int cross_set_upload(cbh_table* t, uint32_t device_index, const cbh_batch
   for (u32 c = 0; c < h->n_columns && c < CBH_CACHE_COLS; ++c) if (shape.side[c]) cs->side |= 1u << c;
   const size_t NH = (size_t)N + M;
   cs->p_roles.resize(N);
-  for (u32 ip = 0; ip < N; ++ip) cs->p_roles[ip] = (u8)h->req_u32[(size_t)CBH_RQ_ROLE_CNT * NH + (x->p_order ? x->p_order[ip] : ip)];   // (<= 4: checked above)
+  for (u32 ip = 0; ip < N; ++ip) cs->p_roles[ip] = (u8)h->req_u32[(size_t)CBH_RQ_ROLE_CNT * NH + (x->p_order ? x->p_order[ip] : ip)];   // (<= CBH_CX_MAX_ROLES: checked above)
   // The halves' OWN actions are not read by any road of a set, but a row that carries more than four of them has no compact
   // record (cbh_compact_scan_kernel) - and the flattener hands the set's A actions to the first row.  A set of action groups
   // therefore uploads the request words with such rows' action counts cleared; a set of up to four actions is uploaded as it is.
+  // Likewise a principal's row with more than four roles: a set of role groups uploads it with the count clamped to four, so that
+  // its record holds the first four roles (the slices were checked by cross_validate; the resources' rows stay as they are).
   cbh_batch hh = *h;
   std::vector<u32> req_copy;
+  if (A > 4 || shape.maxr > 4) req_copy.assign(h->req_u32, h->req_u32 + (size_t)CBH_RQ_NFIELDS * NH);
+  if (shape.maxr > 4) {
+    u32* cnt = req_copy.data() + (size_t)CBH_RQ_ROLE_CNT * NH;
+    for (size_t r = 0; r < N; ++r) cnt[r] = std::min(cnt[r], 4u);
+    hh.req_u32 = req_copy.data();
+  }
   if (A > 4) {
-    req_copy.assign(h->req_u32, h->req_u32 + (size_t)CBH_RQ_NFIELDS * NH);
     u32* cnt = req_copy.data() + (size_t)CBH_RQ_ACT_CNT * NH;
     for (size_t r = 0; r < NH; ++r) if (cnt[r] > 4u && (u64)req_copy[(size_t)CBH_RQ_ACT_OFF * NH + r] + cnt[r] <= (u64)h->n_tuples) cnt[r] = 0;   // (a slice outside the batch stays, to be refused)
     hh.req_u32 = req_copy.data();
@@ -714,7 +745,24 @@ static int cross_set_upload(cbh_table* t, uint32_t device_index, const cbh_batch
   rc |= up(b, cs->d_act, x->action_ids, (size_t)A, s);
   rc |= up(b, cs->d_side, (const u8*)shape.side.data(), (size_t)h->n_columns, s);   // (pageable memory of this frame: the wait below)
   rc |= dalloc(b, d_word, G);
+  const u32 R = cross_role_groups(cs);
+  u32* d_rw = nullptr; u32* d_all = nullptr;
+  if (R > 1) {
+    rc |= up(b, cs->d_role_cnt, h->req_u32 + (size_t)CBH_RQ_ROLE_CNT * NH, (size_t)N, s);   // (the caller's words: the true counts)
+    rc |= dalloc(b, d_rw, (size_t)(R - 1) * N);
+    rc |= dalloc(b, d_all, (size_t)N);
+  }
   if (rc != 0) return drop(-1);
+  if (R > 1) {
+    CrossRoleWordArgs ra{}; ra.role_off = b->dev.req_u32 + (size_t)CBH_RQ_ROLE_OFF * NH; ra.role_cnt = cs->d_role_cnt; ra.roles = b->dev.roles;
+    ra.role_class = rep->dev.role_class; ra.words = d_rw; ra.all = d_all; ra.n = N; ra.groups = R; ra.K = rep->dev.K;
+    hipLaunchKernelGGL(cbh_cross_role_word_kernel, dim3((N + 255u) / 256u), dim3(256), 0, s, ra);
+    cs->role_words = d_rw; cs->rc_all = d_all;
+    std::vector<CrossRoleGroup> recs(R);   // (pageable memory of this frame: the wait below)
+    const u32 open_from = cross_open_from(rep->dev, cs);
+    for (u32 g = 0; g < R; ++g) recs[g] = CrossRoleGroup{g ? d_rw + (size_t)(g - 1u) * N : nullptr, d_all, cs->d_role_cnt, g, open_from};
+    if (up(b, cs->d_rg, recs.data(), (size_t)R, s) != 0 || hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); fail("cbh_cross_upload: upload failed"); return drop(-1); }
+  }
   CrossActWordArgs wa{}; wa.action_ids = cs->d_act; wa.action_class = rep->dev.action_class; wa.out = d_word; wa.a = A; wa.K = rep->dev.K;
   hipLaunchKernelGGL(cbh_cross_act_word_kernel, dim3(1), dim3(64), 0, s, wa);
   if (hipGetLastError() != hipSuccess || hipMemcpyAsync(cs->act_words.data(), d_word, (size_t)G * 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
@@ -769,11 +817,16 @@ static int cross_set_check(cbh_table* t, cbh_cross_set* cs, const cbh_params* p,
   x.n = cs->n; x.r_begin = r_begin; x.n_tile = (u32)nt; x.words = (u32)W; x.side = cs->side;
   const TableDev& dev = rep->dev;
   const size_t lds = cbh_plan_lds(pl, dev.flags, dev.max_depth, dev.n_scopes, dev.K, ka.b.n_columns, dev.inline_cols, dev.n_dr, false, CBH_W2_NA, true) + lds_pad();
-  // one launch per group of four actions, each with the group's word and its own planes [4 g, 4 g + 4) of the block
+  // one launch per group of four actions, each with the group's word and its own planes [4 g, 4 g + 4) of the block - and within it
+  // one per group of four roles, in order: group 0 stores its ballots, every later one ORs into them what the earlier ones left open
+  const u32 R = cross_role_groups(cs);
   for (u32 g = 0; g < cross_groups(cs); ++g) {
     x.act_word = cs->act_words[g];
     x.allow = cs->planes + (size_t)4 * g * W; x.flagged = flagged ? cs->planes + per + (size_t)4 * g * W : nullptr;
-    hipLaunchKernelGGL(fn, dim3((u32)((nt + pl.threads - 1) / pl.threads)), dim3(pl.threads), lds, s, ka, (const KernelArgs*)nullptr, x);   // (the arguments in memory are the evaluator call's: no _x kernel has one)
+    for (u32 rg = 0; rg < R; ++rg) {
+      x.rg = cs->d_rg ? cs->d_rg + rg : nullptr;   // (null in a set without role groups: exactly the launch such a set always had)
+      hipLaunchKernelGGL(fn, dim3((u32)((nt + pl.threads - 1) / pl.threads)), dim3(pl.threads), lds, s, ka, (const KernelArgs*)nullptr, x);   // (the arguments in memory are the evaluator call's: no _x kernel has one)
+    }
   }
   HIPCHK(hipGetLastError());
   for (int which = 0; which < (flagged ? 2 : 1); ++which) {
@@ -795,9 +848,10 @@ extern "C" const char* cbh_cross_describe(cbh_table* t, cbh_cross_set* cs, const
     if (cs->b->table != t) s = "none: the set was uploaded for a different table";
     else if (!cross_kernel_for(cs, p->flags, pl)) s = "none: these flags choose a plan without a direct form";
     else {
-      char m[128], g[40] = "";
+      char m[160], g[40] = "", r[40] = "";
       if (cross_groups(cs) > 1) snprintf(g, sizeof g, ", %u action groups", cross_groups(cs));
-      snprintf(m, sizeof m, "[direct cross, %u + %u rows, narrow columns 0x%x%s]", cs->n, cs->m, cs->b->dev.compact_info & CBH_CI_NARROW_MASK, g);
+      if (cross_role_groups(cs) > 1) snprintf(r, sizeof r, ", %u role groups", cross_role_groups(cs));
+      snprintf(m, sizeof m, "[direct cross, %u + %u rows, narrow columns 0x%x%s%s]", cs->n, cs->m, cs->b->dev.compact_info & CBH_CI_NARROW_MASK, g, r);
       s = std::string(cbh_flat_cross_name(pl.kernel)) + m;
     }
   } catch (...) { return ""; }
@@ -840,12 +894,20 @@ static int cross_pairs_upload(cbh_table* t, cbh_cross_set* cs, const uint32_t* p
   const BatchDev& hd = hb->dev;
   const u32 ncol = hd.n_columns;
   b->max_actions = (u32)A; b->max_roles = maxr; b->plain_tags = cs->plain;   // (every row of a set holds plain values)
-  b->wide_lo = 0; b->wide_hi = A > CBH_W2_NA ? n_pairs : 0;                  // (no principal of a set has more than four roles)
+  // where the requests wider than the walk's base shape lie (validate_batch's wide_lo / wide_hi): every pair of a set of more than
+  // CBH_W2_NA actions, else the pairs whose principal has more than CBH_W2_NR roles (a set with role groups)
+  b->wide_lo = 0; b->wide_hi = A > CBH_W2_NA ? n_pairs : 0;
+  if (A <= CBH_W2_NA && maxr > CBH_W2_NR) {
+    u32 wlo = n_pairs, whi = 0;
+    for (u32 q = 0; q < n_pairs; ++q) if (cs->p_roles[pair_p[q]] > CBH_W2_NR) { if (wlo == n_pairs) wlo = q; whi = q + 1; }
+    b->wide_lo = wlo; b->wide_hi = whi;
+  }
   BatchDev& d = b->dev;
   batch_set_counts(b, n_pairs, (u32)(NP * A), hd.n_roles, ncol, hd.n_strings, hd.heap_len);
   hipStream_t s = b->stream;
   CrossGatherArgs ga{};
   ga.h_req = hd.req_u32; ga.h_tag = hd.col_tag; ga.h_val = hd.col_val; ga.p_order = cs->p_order; ga.r_order = cs->r_order; ga.col_side = cs->d_side;
+  ga.p_role_cnt = cs->d_role_cnt;   // (a set with role groups: the true counts; else null - the request words')
   ga.n = cs->n; ga.nh = cs->n + cs->m; ga.n_pairs = n_pairs; ga.a = (u32)A; ga.n_columns = ncol;
   CrossArgs ca{};   // (for cbh_cross_actions_kernel: a product of n_pairs x 1)
   ca.n = n_pairs; ca.m = 1; ca.a = (u32)A; ca.action_ids = cs->d_act;

@@ -323,8 +323,18 @@ int cbh_result_download_allow_bits(cbh_table* t, cbh_device_batch* b, uint64_t* 
  *                         role: ask for `flagged`, and see cbh_cross_pairs_upload.
  *   CBH_CX_ACTION_GROUPS  5 .. CBH_MAX_ACTIONS_PER_REQUEST actions, decided four at a time: (A + 3) / 4 launches of the same kernel per
  *                         check, one download.  The planes stay [A][words_per_plane], action-major, for every A.
+ *   CBH_CX_ROLE_GROUPS    principals with 5 .. CBH_CX_MAX_ROLES roles, decided four roles at a time: a check launches the same kernel
+ *                         (maxr + 3) / 4 times per group of four actions - ((maxr + 3) / 4) * ((A + 3) / 4) launches in all, in
+ *                         order on the set's stream, one download; maxr = the role count of the set's widest principal.  The
+ *                         launch of a later role group decides only what the earlier ones left open (an action no earlier role
+ *                         allowed) and a wave without a principal of that many roles returns at once: order the principals by role
+ *                         count - cerbos_amd.cross.cross_halves(sort=True) does - and the wide ones share their waves.  The
+ *                         planes are the same two bits per tuple as for a narrow set, `flagged` bit for bit the status of the
+ *                         materialised product (where that product's kernels mark an error of a derived-role definition on
+ *                         the actions still open rather than on every action of the request, so do the planes).  (16, not 4 or 8: those values of `accept`
+ *                         were refused as unknown bits before this one existed, and still are.)
  * Without its bit such a set returns 1, as every set without a direct form: a table that is not flat, a principal with more than
- * four roles, a field of the halves that does not fit the compact record, an attribute value that needs the evaluator (an int, uint,
+ * CBH_CX_MAX_ROLES roles (with CBH_CX_ROLE_GROUPS; more than four without), a field of the halves that does not fit the compact record, an attribute value that needs the evaluator (an int, uint,
  * list or map in a column a classified leaf compares: the `_any` kernels), a table with membership leaves or other conditions
  * outside the classified leaves that is decided by the mask walk (long buckets: cbh_check_flat_kernel_any_masks has no direct form).
  * cbh_cross_upload(t, i, halves, x, out) is cbh_cross_upload_ex(t, i, halves, x, 0, out).
@@ -337,14 +347,14 @@ int cbh_result_download_allow_bits(cbh_table* t, cbh_device_batch* b, uint64_t* 
  * or more, words_per_plane < W, a failed allocation or copy - the set stays usable), nothing is written for a refused argument;
  * 1 = these flags choose a plan without a direct form (CBH_F_STRICT_EVALUATION, CBH_F_WANT_EFFECTIVE_POLICIES).
  * CBH_F_LENIENT_SCOPE_SEARCH is served.  Calls on one set queue in call order; the result words on the device are reused
- * from tile to tile.  cbh_cross_describe: the kernel a check with these flags would launch (and ", G action groups" where it
- * launches it more than once), or "none: ..." .
+ * from tile to tile.  cbh_cross_describe: the kernel a check with these flags would launch (and ", G action groups" and
+ * ", R role groups" where it launches it more than once), or "none: ..." .
  *
  * The full answer of chosen pairs - the flagged ones: cbh_cross_pairs_upload builds, on the device and from the set's own rows, the
  * resident batch of n_pairs requests x A actions in which request q pairs device principal pair_p[q] (< N) with device resource
  * pair_r[q] (< M): the set's device orders, i.e. bit q of a tile's plane decodes to pair_r = r_begin + q / N, pair_p = q % N.
  * Duplicates are allowed.  The batch is a resident batch like any other, with the shape a host-built batch of those requests
- * would get: cbh_check_resident, cbh_result_download, cbh_batch_set_trail / cbh_trail_download, cbh_batch_release; it does not
+ * would get (a principal of more than four roles brings all of them: the walk's kernels decide such a batch): cbh_check_resident, cbh_result_download, cbh_batch_set_trail / cbh_trail_download, cbh_batch_release; it does not
  * depend on the set afterwards.  < 0: a null argument, an index out of range (checked before anything is launched), n_pairs of 0,
  * n_pairs * A of 2^32 or more, a set of another table, a failed allocation or copy.
  * Not here: one set sharded over several devices (split the resources); trails and the trace pass directly on a set (take the
@@ -353,6 +363,9 @@ int cbh_result_download_allow_bits(cbh_table* t, cbh_device_batch* b, uint64_t* 
 #define CBH_HAS_CROSS_DIRECT_EX 1
 #define CBH_CX_DERIVED_ROLES 1u   /* accept a flat table with derived roles */
 #define CBH_CX_ACTION_GROUPS 2u   /* accept 5 .. CBH_MAX_ACTIONS_PER_REQUEST actions, decided four at a time */
+#define CBH_HAS_CROSS_ROLE_GROUPS 1
+#define CBH_CX_ROLE_GROUPS 16u    /* accept principals with 5 .. CBH_CX_MAX_ROLES roles, decided four roles at a time */
+#define CBH_CX_MAX_ROLES 16u
 typedef struct cbh_cross_set cbh_cross_set;
 int cbh_cross_upload(cbh_table* t, uint32_t device_index, const cbh_batch* halves, const cbh_cross* x, cbh_cross_set** out);
 int cbh_cross_upload_ex(cbh_table* t, uint32_t device_index, const cbh_batch* halves, const cbh_cross* x, uint32_t accept, cbh_cross_set** out);

@@ -25,6 +25,11 @@ same, so it must not differ).
                                                    actions go direct through cbh_cross_upload_ex (every `accept` bit set); A > 4 takes
                                                    the workload's further actions, then names no policy knows.  --skip-host: without
                                                    the host leg (numpy lays out N * M * A on the host: minutes at 4096 x 1024 x 16)
+  python tools/cross_bench.py --skip-host --configs c2:4096:1024:r8
+                                                   a last field rR gives EVERY principal R roles (5 .. 16): the workload's own first,
+                                                   then roles no policy names, then one role an ALLOW rule names - the deciding
+                                                   role sits in the last group of four.  The direct legs pass every `accept` bit,
+                                                   CX_ROLE_GROUPS among them; the device leg's product takes the walk's kernels
   python tools/cross_bench.py --check-alone c3:4096:1024
                                                    the direct check alone (inputs resident, planes copied to the host), one line: for an
                                                    A/B of two builds or switches (CBH_CROSS_DR_MEMO=0), one process per repetition
@@ -84,16 +89,41 @@ def timed(table, reps, warmup, body):
     return out
 
 
+ACCEPT = capi.CX_ALL | capi.CX_ROLE_GROUPS
+ROLES = [None]   # the rR suffix of the configuration being run (parse)
+
+
 def parse(cfg):
-    """NAME:N:M[:A] -> (name, n, m, a or None)"""
+    """NAME:N:M[:A][:rR] -> (name, n, m, a or None); R is left in ROLES for setup"""
     f = cfg.split(":")
+    ROLES[0] = int(f.pop()[1:]) if f[-1].startswith("r") else None
     return f[0], int(f[1]), int(f[2]), (int(f[3]) if len(f) > 3 else None)
 
 
+def widen(docs, principals, r):
+    """every principal with r roles: its own first, roles no policy names, and last a role an ALLOW rule names (one it does not hold
+    yet, else its own last role moved there)"""
+    allowing = []
+    for d in docs:
+        for rule in d.get("resourcePolicy", {}).get("rules", []):
+            if rule.get("effect") == "EFFECT_ALLOW":
+                allowing += [x for x in rule.get("roles", []) if x not in allowing and x != "*"]
+    out = []
+    for p in principals:
+        own = list(p["roles"])[:r - 1]
+        new = [x for x in allowing if x not in own]
+        last = new[0] if new else own.pop()
+        out.append(dict(p, roles=own + ["norole%02d" % i for i in range(r - 1 - len(own))] + [last]))
+    return out
+
+
 def setup(name, n, m, a=None):
-    lt = lower_rule_table(rule_table_from_policies(policies_from_docs(getattr(workloads, name + "_policies")())))
+    docs = getattr(workloads, name + "_policies")()
+    lt = lower_rule_table(rule_table_from_policies(policies_from_docs(docs)))
     ins = getattr(workloads, name + "_requests")(n + m, seed=17).to_inputs()
     principals, resources, actions = [i["principal"] for i in ins[:n]], [i["resource"] for i in ins[n:]], list(ins[0]["actions"])
+    if ROLES[0]:
+        principals = widen(docs, principals, ROLES[0])
     if a is not None:     # the workload's own actions first, then its further ones, then names no policy knows
         more = [x for x in getattr(workloads, name.upper() + "_ACTIONS", []) if x not in actions]
         actions = (actions + more + ["unknown%02d" % i for i in range(64)])[:a]
@@ -124,7 +154,7 @@ def device_leg(lt, table, fl, p, r, a):
 
 def direct_leg(lt, table, fl, p, r, a):
     def body():
-        cs = cross.cross_direct_upload(table, fl, lt.columns, p, r, a, accept=capi.CX_ALL)
+        cs = cross.cross_direct_upload(table, fl, lt.columns, p, r, a, accept=ACCEPT)
         if cs is None:
             raise SystemExit("the set has no direct form")
         cs.check(0, len(r), now_ns=NOW)
@@ -156,9 +186,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--configs", default="c2:1024:1024,c2:4096:1024,t:1024:1024,t:4096:1024")
     ap.add_argument("--profile", default=None, metavar="NAME:N:M")
-    ap.add_argument("--profile-direct", default=None, metavar="NAME:N:M")
+    ap.add_argument("--profile-direct", default=None, metavar="NAME:N:M[:A][:rR]")
     ap.add_argument("--skip-host", action="store_true")
-    ap.add_argument("--check-alone", default=None, metavar="NAME:N:M[:A]")
+    ap.add_argument("--check-alone", default=None, metavar="NAME:N:M[:A][:rR]")
     ap.add_argument("--pairs", default=None, metavar="NAME:N:M:COUNT")
     args = ap.parse_args()
     if args.reps < 10:
@@ -192,9 +222,8 @@ def main():
         table.close()
         return
     if args.profile_direct:
-        name, n, m = args.profile_direct.split(":")
-        n, m = int(n), int(m)
-        lt, table, fl, p, r, a = setup(name, n, m)
+        name, n, m, na = parse(args.profile_direct)
+        lt, table, fl, p, r, a = setup(name, n, m, na)
         cs = direct_leg(lt, table, fl, p, r, a)()
         print(json.dumps({"profile_direct": args.profile_direct, "kernel": cs.describe(), "columns": len(lt.columns),
                           "plane_bytes_written": len(a) * ((n * m + 63) // 64) * 8}))
@@ -233,7 +262,7 @@ def main():
             dev_t, dir_t = timed_alternating(table, args.reps, args.warmup, [device_leg(lt, table, fl, p, r, a), direct_leg(lt, table, fl, p, r, a)])
             line["device_leg"] = stats(dev_t, decisions)
             line["direct_leg"] = stats(dir_t, decisions)
-            cs = cross.cross_direct_upload(table, fl, lt.columns, p, r, a, accept=capi.CX_ALL)
+            cs = cross.cross_direct_upload(table, fl, lt.columns, p, r, a, accept=ACCEPT)
             line["direct_kernel"] = cs.describe()
 
             def check_alone():
