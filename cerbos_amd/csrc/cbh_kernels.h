@@ -110,7 +110,10 @@ __global__ __launch_bounds__(CBH_BLOCK) void cbh_resolve_globs_kernel(TableDev t
           carry = adv >> 63;
         }
       }
-      // epsilon closure over star positions (a star may match the empty string)
+      // epsilon closure over star positions (a star may match the empty string).  A round carries a state over ONE star
+      // position; the lowering collapses runs of adjacent stars (lower/globs.py _collapse_stars, asserted in GlobNFA), so no
+      // star position follows another: the first round completes the closure, the second finds nothing and leaves.  The cap
+      // of 8 is never reached - a table with a run of nine stars would be decided wrongly here, and is never built.
       for (int it = 0; it < 8; ++it) {
         u64 c2 = 0; bool changed = false;
 #pragma unroll

@@ -121,12 +121,27 @@ def _parse_seq(pat: str, i: int, closers: str):
     return seqs, i
 
 
+def _collapse_stars(seq):
+    """Adjacent star elements become one: a run that holds a ``**`` is one ``**``, a run of ``*`` alone one ``*`` (the union
+    of the sets, starred once, is the same language).  The device's closure loop relies on it: no star position follows
+    another, so one round reaches everything (cbh_kernels.h, cbh_resolve_globs_kernel)."""
+    out = []
+    for el in seq:
+        if el[0] == "S" and out and out[-1][0] == "S":
+            if len(el[1]) > len(out[-1][1]):
+                out[-1] = el
+        else:
+            out.append(el)
+    return out
+
+
 def parse_glob(pattern: str):
-    """Pattern text (already through fix_glob) -> list of linear element sequences."""
+    """Pattern text (already through fix_glob) -> list of linear element sequences, star runs collapsed (alternatives are
+    expanded first: ``*{*,a}`` has a run only in one of its sequences)."""
     seqs, i = _parse_seq(pattern, 0, "")
     if i != len(pattern):
         raise GlobError("unexpected %r" % pattern[i])
-    return seqs
+    return [_collapse_stars(s) for s in seqs]
 
 
 class GlobNFA:
@@ -173,6 +188,9 @@ class GlobNFA:
         self.words = (self.nbits + 63) // 64
         if self.words > self.MAX_WORDS:
             raise GlobError("glob automaton needs %d state words (max %d)" % (self.words, self.MAX_WORDS))
+        # no star position follows another (parse_glob collapses runs; a sequence ends on its accept position, which is no
+        # star): the closure is complete after ONE round, and the device's loop of at most eight rounds relies on it
+        assert not self.star & (self.star << 1), "adjacent star positions"
         self.init = self._closure(self.init)
 
     def _closure(self, a: int) -> int:
