@@ -458,9 +458,53 @@ __device__ __forceinline__ u64 load_u64g(const CBH_G u32* p) {   // 8-byte align
 // wave-uniform as before (a record's, a scope's definition's); on a miss the outcome is computed for EVERY lane - each lane has its
 // pair's two rows in its slice of the column cache, and a lane beyond the tile's end shadows pair 0 with no role and no action, so
 // what the memo keeps for it is a real pair's outcome that nothing reads.
-template <bool WITH_CALL, int MODE, bool EP = false, bool MEMO = false, bool COMPACT = false, bool CROSS = false>
-__device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c, const CrossDev& x = CrossDev{}) {
+// (THE SAME RULE stands spelled out in flat_body's CROSS branch, whose `_x` kernels keep the machine code they were measured with: a
+// change here is a change there, and tests/test_cross_direct_roles.py holds that copy against the general walk bit for bit as
+// tests/test_flat_action_groups.py holds this one.)
+// The general walk's marks for the error of a derived-role definition, on a lane's four status bytes: action k where an error (dmask:
+// bit d a CEL error at chain position d, bit 16 + d one outside the device subset) lies below the deepest position a legitimate walk
+// of k reached (legit, done: bit 4 r + k; dp0 .. dp3: the bit planes of the depth a walk was decided at).
+__device__ __forceinline__ u32 flat_mark_each(u32 st4, u32 dmask, u32 legit, u32 done, u32 dp0, u32 dp1, u32 dp2, u32 dp3) {
+  u32 e1 = 0, u1 = 0;
+#pragma unroll
+  for (u32 k = 0; k < 4; ++k) {
+    const u32 lk = legit & (0x1111u << k);
+    u32 below = 0;   // the chain positions a legitimate walk of action k reached, as a mask
+    if (lk & ~done) below = 0xFFFFu;
+    else if (lk) {
+      u32 cand = lk, d = 0;
+      u32 tp = cand & dp3; if (tp) { cand = tp; d |= 8u; }
+      tp = cand & dp2; if (tp) { cand = tp; d |= 4u; }
+      tp = cand & dp1; if (tp) { cand = tp; d |= 2u; }
+      tp = cand & dp0; if (tp) { cand = tp; d |= 1u; }
+      below = (2u << d) - 1u;
+    }
+    e1 |= (dmask & below) ? 1u << (8u * k) : 0u;
+    u1 |= ((dmask >> 16) & below) ? 1u << (8u * k) : 0u;
+  }
+  const u32 un = (st4 >> 1) & ~st4 & 0x01010101u;   // bytes that read 2
+  const u32 em = (e1 & ~un) * 0xFFu, um = u1 * 0xFFu;
+  st4 = (st4 & ~em) | (em & 0x01010101u);
+  return (st4 & ~um) | (um & 0x02020202u);
+}
+// AGROUP: one of the launches that decide a batch of wide requests (5 .. CBH_MAX_ACTIONS_PER_REQUEST actions, at most four roles) four
+// actions at a time (cbh_check_walk2.h CbhPlan.groups; cbh_host_resident.h launch_plan): launch g decides the actions 4 g .. 4 g + 3 of
+// every request that has them - its lane's action count is clamp(ACT_CNT - 4 g, 0, 4), its ids and its stores lie at ACT_OFF + 4 g.
+// Effect, policy, scope and a tuple's own status depend on that action alone.  Two facts are the request's: `edr` - group 0 stores
+// it, a later group ORs in what ITS legitimate walks reached (the union over the groups is the request's) - and the error of a
+// derived-role DEFINITION, which the road these batches took before marks in two ways (FlatGroupDev.each_from).  A lane without an
+// action in its group stands at no scope: a wave of such lanes walks nothing and stores nothing (it does run the prologue, whose
+// barrier the rest of the workgroup reaches).
+struct FlatGroupDev {
+  CBH_G u8* dflag;   // [request]: bit 0 a definition's CEL error, bit 1 one outside the device subset, ORed in by every group for
+                     // cbh_flat_group_status_kernel; null = nothing to keep (a table without derived roles, a call that does not want them)
+  u32 group;         // g
+  u32 each_from;     // a request of at least this many actions gets the general walk's marks, per action; a narrower one the walk kernels', on every action
+};
+template <bool WITH_CALL, int MODE, bool EP = false, bool MEMO = false, bool COMPACT = false, bool CROSS = false, bool AGROUP = false>
+__device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c, const CrossDev& x = CrossDev{}, const FlatGroupDev& ag = FlatGroupDev{}) {
   static_assert(!CROSS || (COMPACT && !WITH_CALL && !EP), "the direct cross form: compact inputs, no evaluator call, no trail");
+  static_assert(!AGROUP || (!COMPACT && !CROSS && !EP), "an action-group launch: the wide inputs, no trail");
   constexpr bool STAGED = MODE == 1;
   constexpr u32 BTYPE = MODE == 2 ? (u32)CBH_B_RESSEG : (u32)CBH_B_RESOURCE;
   const TableDev& t = ka_regs.t;
@@ -494,6 +538,7 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c, con
   bool spec = false; u32 spec_ix = 0;
   u32 x_prow = 0, x_rrow = 0;   // CROSS: the lane's two rows of the halves
   u32 x_done = 0;               // CROSS, role group >= 1: bit k = an earlier group's role allowed action k
+  u32 act_total = 0;            // AGROUP: the request's action count (act_cnt is the group's)
   if constexpr (CROSS) {
     // ---- the pair (cbh_cross.h: resource-major, q = j' * N + i').  A lane beyond the tile's end shadows q = 0 with no action and no role.
     const u32 jp = req / x.n, ip = req - jp * x.n;
@@ -546,6 +591,11 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c, con
   role_off = RQ(CBH_RQ_ROLE_OFF); act_off = RQ(CBH_RQ_ACT_OFF);
   role_cnt = valid ? RQ(CBH_RQ_ROLE_CNT) : 0; act_cnt = valid ? RQ(CBH_RQ_ACT_CNT) : 0;   // both <= 4 (host-checked)
 #undef RQ
+  if constexpr (AGROUP) {   // the group's slice of the request's actions (act_total: the request's own count)
+    act_total = act_cnt;
+    const u32 g4 = 4u * ag.group, left = act_cnt > g4 ? act_cnt - g4 : 0u;
+    act_cnt = left < 4u ? left : 4u; act_off += g4;
+  }
   // ---- the request's loads, in TWO round trips to memory.  First trip, all issued back to back and depending on nothing: the
   // request words above, the four action ids (speculated, below), this thread's bytes of the two class tables, the tag bytes of
   // the cached columns (cc_load_tags).  Second trip, issued when the request words are in: the role ids and every column's
@@ -556,9 +606,11 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c, con
   // Actions: a batch of four-action requests laid out back to back has ACT_OFF = 4 * request - read the four ids from
   // there with ONE 16-byte load that does not wait for ACT_OFF to arrive, and fall back to the dependent loads for the
   // lanes where the guess was wrong.  (Unconditional: without four tuples the load reads request words and is not used.)
+  if constexpr (!AGROUP) {   // (a batch of wide requests is not laid out four to a request: the ids are loaded where ACT_OFF says)
   spec = b.n_tuples >= 4u;   // wave-uniform
   spec_ix = (4u * req + 4u <= b.n_tuples) ? 4u * req : 0u;
   sp = load_u32x4(spec ? b.tuple_action + spec_ix : b.req_u32);
+  }
   const u32 cls_i = threadIdx.x < t.K ? threadIdx.x : kmax;
   cls_a0 = (t.K ? t.action_class : (const CBH_G u8*)b.req_u32)[cls_i]; cls_r0 = (t.K ? t.role_class : (const CBH_G u8*)b.req_u32)[cls_i];
   }
@@ -612,7 +664,9 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c, con
   if constexpr (CROSS) cc_fill_cross(c, b, NR, x_prow, x_rrow, x.side); else if constexpr (COMPACT) cc_fill_compact(c, b, NR, w0, wd); else cc_fill(c, b, NR, w0, wd, cct);   // (behind every LDS store of this prologue)
   // ... and the chain's first scope (ruletable.go:848-882; per lane, reads the scope tables): its load goes out with the second trip
   const bool lenient = (flags & CBH_F_LENIENT_SCOPE_SEARCH) != 0;
-  const u32 first = chain_first(t, r_scope, FLAG_RES, lenient);
+  // (AGROUP, a later group: a lane whose request has no action in it stands at no scope - it takes no part in the walk or in the second climb)
+  const u32 first_own = chain_first(t, r_scope, FLAG_RES, lenient);
+  const u32 first = (AGROUP && ag.group != 0u && act_cnt == 0u) ? CBH_NONE : first_own;
   if constexpr (COMPACT) {
   } else if (cls_in_lds) {
     __syncthreads();
@@ -1145,7 +1199,10 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c, con
           u32 lv = 1u;
           if (dx.cond != CBH_NONE) lv = leafish_memo(dx.cond, dx.flags & 3u, [&] { return dx.leaf; }, applies);
           if constexpr (CROSS) { if (applies) dmask |= (((lv & 2u) >> 1) | ((lv & 8u) << 13)) << d2; } else
-          if (applies) { if (lv & 1u) edr |= 1ull << dx.name; derr = derr || (lv & 2u) != 0; dr_unsup = dr_unsup || (lv & 8u) != 0; }
+          if (applies) {
+            if (lv & 1u) edr |= 1ull << dx.name; derr = derr || (lv & 2u) != 0; dr_unsup = dr_unsup || (lv & 8u) != 0;
+            if constexpr (AGROUP) dmask |= (((lv & 2u) >> 1) | ((lv & 8u) << 13)) << d2;   // (by chain position as well, for a request of each_from actions)
+          }
         }
       }
       const u32 up = uchain_next(t, uload(&t.scope_parent[g_si]), FLAG_RES);
@@ -1159,7 +1216,7 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c, con
       // principal of that many roles (CrossRoleGroup.open_from: the host knows the product's plan) gets the general walk's marks:
       // action k where an error lies below the deepest position a legitimate walk of k reached.
       if (x.rg) {
-        if (dmask != 0 && x.rg->p_role_cnt[x_prow] >= x.rg->open_from) {
+        if (dmask != 0 && x.rg->p_role_cnt[x_prow] >= x.rg->open_from) {   // (flat_mark_each's rule, spelled out - keep the two copies in step: the `_x` kernels keep the machine code they were measured with)
           u32 e1 = 0, u1 = 0;
 #pragma unroll
           for (u32 k = 0; k < 4; ++k) {
@@ -1184,6 +1241,16 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c, con
           derr = false; dr_unsup = false;
         }
       }
+    }
+    if constexpr (AGROUP) {
+      // The same choice by the request's own action count (FlatGroupDev.each_from: the host knows which kernel decided such a request
+      // before).  The general walk's marks are per action and need nothing of the other groups; the walk kernels' lie on EVERY action
+      // of the request, other groups' included: the lane marks its own four below and leaves the two facts in the request's byte,
+      // from which cbh_flat_group_status_kernel marks the request's tuples behind the last group.
+      if (dmask != 0 && act_total >= ag.each_from) {
+        st4 = flat_mark_each(st4, dmask, legit, done, dp0, dp1, dp2, dp3);
+        derr = false; dr_unsup = false;
+      } else if ((derr || dr_unsup) && ag.dflag) ag.dflag[req] |= (u8)((derr ? 1u : 0u) | (dr_unsup ? 2u : 0u));
     }
     if (derr) {   // evaluation errors are a per-request fact: every action that is not UNSUPPORTED
       const u32 un = (st4 >> 1) & ~st4 & 0x01010101u;   // bytes that read 2
@@ -1216,6 +1283,9 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c, con
   // (compact form: only the stores need the offset - a load up here, inside a uniform branch, would be waited for in the prologue)
   if constexpr (COMPACT) { if (!(b.compact_info & CBH_CI_ACT4)) act_off = b.req_u32[(size_t)CBH_RQ_ACT_OFF * NR + req]; }
   const bool packed = valid && act_cnt == 4 && (act_off & 3u) == 0;
+  if constexpr (AGROUP) {   // the request's derived roles: group 0 stores them, a later group ORs in what its own walks reached
+    if (valid && o.edr) { if (ag.group == 0u) o.edr[req] = edr; else if (act_cnt != 0u && edr != 0ull) o.edr[req] |= edr; }
+  }
 #ifndef CBH_HOSTSIM
   typedef u32 u32x4 __attribute__((ext_vector_type(4)));
 #else
@@ -1230,11 +1300,11 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c, con
     for (u32 k = 0; k < 4; ++k)   // NO_MATCH -> DENY (check.go:451-453)
       pw[k] = (u32)(alw[k] ? CBH_EFFECT_ALLOW : CBH_EFFECT_DENY) | (((st4 >> (8 * k)) & 0xFFu) << 2) | (won[k] ? pk_hit : pk_none) | (sc1[k] << sh);
     if (packed) {
-      if (o.edr) store_nt(o.edr + req, edr);
+      if (!AGROUP && o.edr) store_nt(o.edr + req, edr);
       u32x4 v; v.x = pw[0]; v.y = pw[1]; v.z = pw[2]; v.w = pw[3];
       store_nt((CBH_G u32x4*)(o.policy + act_off), v);
     } else if (valid) {
-      if (o.edr) o.edr[req] = edr;
+      if (!AGROUP && o.edr) o.edr[req] = edr;
 #pragma unroll
       for (u32 k = 0; k < 4; ++k) if (k < act_cnt) o.policy[act_off + k] = pw[k];
     }
@@ -1254,13 +1324,13 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c, con
     }
 #endif
     if (packed) {
-      if (o.edr) store_nt(o.edr + req, edr);
+      if (!AGROUP && o.edr) store_nt(o.edr + req, edr);
       store_nt((CBH_G u32*)(o.effect + act_off), eff4);
       if (o.status) store_nt((CBH_G u32*)(o.status + act_off), st4);
       if (o.policy) { u32x4 v; v.x = pol[0]; v.y = pol[1]; v.z = pol[2]; v.w = pol[3]; store_nt((CBH_G u32x4*)(o.policy + act_off), v); }
       if (o.scope) { u32x4 v; v.x = scp[0]; v.y = scp[1]; v.z = scp[2]; v.w = scp[3]; store_nt((CBH_G u32x4*)(o.scope + act_off), v); }
     } else if (valid) {
-      if (o.edr) o.edr[req] = edr;
+      if (!AGROUP && o.edr) o.edr[req] = edr;
 #pragma unroll
       for (u32 k = 0; k < 4; ++k) {
         if (k < act_cnt) {
@@ -1345,6 +1415,48 @@ CBH_FLAT_TRAIL_KERNEL(cbh_check_flat_trail_kernel_staged, 5, false, 1)
 CBH_FLAT_TRAIL_KERNEL(cbh_check_flat_trail_kernel_any_staged, 3, true, 1)
 CBH_FLAT_TRAIL_KERNEL(cbh_check_flat_trail_kernel_masks, 3, false, 2)
 CBH_FLAT_TRAIL_KERNEL(cbh_check_flat_trail_kernel_any_masks, 3, true, 2)
+// The seven wide-input kernels once more as action-group launches (flat_body AGROUP), the group's arguments a by-value parameter of
+// their own: a batch of requests with 5 .. CBH_MAX_ACTIONS_PER_REQUEST actions and at most four roles is decided by (max_actions + 3) / 4
+// launches of one of them, in order on the batch's stream.  Same attributes as their four-action siblings.
+typedef void (*cbh_group_kernel_fn)(const KernelArgs, const KernelArgs*, const FlatGroupDev);
+#define CBH_FLAT_GROUP_KERNEL(NAME, MINW, CALL, MODE, MEMO)                                                                     \
+  __global__ CBH_FLAT_ATTRS(MINW) void NAME(const KernelArgs a, const KernelArgs* __restrict__ ka, const FlatGroupDev ag) {    \
+    CBH_FLAT_CTX(a, ka);                                                                                                        \
+    flat_body<CALL, MODE, false, MEMO, false, false, true>(a, c, CrossDev{}, ag);                                                \
+  }
+CBH_FLAT_GROUP_KERNEL(cbh_check_flat_kernel_g, 7, false, 0, false)
+CBH_FLAT_GROUP_KERNEL(cbh_check_flat_kernel_dr_g, 7, false, 0, true)
+CBH_FLAT_GROUP_KERNEL(cbh_check_flat_kernel_any_g, 4, true, 0, false)
+CBH_FLAT_GROUP_KERNEL(cbh_check_flat_kernel_staged_g, 5, false, 1, false)
+CBH_FLAT_GROUP_KERNEL(cbh_check_flat_kernel_any_staged_g, 4, true, 1, false)
+CBH_FLAT_GROUP_KERNEL(cbh_check_flat_kernel_masks_g, 4, false, 2, false)
+CBH_FLAT_GROUP_KERNEL(cbh_check_flat_kernel_any_masks_g, 3, true, 2, false)
+// the action-group instantiation of the kernel a plan picks (never null for one of the seven: a missing kernel is an error, not a fallback)
+static inline cbh_group_kernel_fn cbh_flat_group_variant(cbh_check_kernel_fn fn) {
+  return fn == cbh_check_flat_kernel ? cbh_check_flat_kernel_g : fn == cbh_check_flat_kernel_dr ? cbh_check_flat_kernel_dr_g
+       : fn == cbh_check_flat_kernel_any ? cbh_check_flat_kernel_any_g : fn == cbh_check_flat_kernel_staged ? cbh_check_flat_kernel_staged_g
+       : fn == cbh_check_flat_kernel_any_staged ? cbh_check_flat_kernel_any_staged_g : fn == cbh_check_flat_kernel_masks ? cbh_check_flat_kernel_masks_g
+       : fn == cbh_check_flat_kernel_any_masks ? cbh_check_flat_kernel_any_masks_g : nullptr;
+}
+// Behind the last group of a table with derived roles: the error of a derived-role definition that some group met (FlatGroupDev.dflag)
+// onto EVERY tuple of its request, by flat_body's own rule for a four-action request - a CEL error on every action that is not
+// UNSUPPORTED, "outside the device subset" on all.  One lane per request of [lo, hi); the requests of each_from actions or more were
+// marked per action by their own launches and left no flag.  `packed`: the results are packed words (CBH_FI_PACKED_RES).
+struct FlatGroupStatusArgs { const CBH_G u32* req_u32; const CBH_G u8* dflag; CBH_G u8* status; CBH_G u32* packed; u32 n_requests, lo, hi, pad; };
+__global__ __launch_bounds__(256) void cbh_flat_group_status_kernel(FlatGroupStatusArgs a) {
+  const u32 r = a.lo + blockIdx.x * 256u + threadIdx.x;
+  if (r >= a.hi) return;
+  const u32 f = a.dflag[r];
+  if (f == 0u) return;
+  const size_t NR = a.n_requests;
+  const u32 off = a.req_u32[(size_t)CBH_RQ_ACT_OFF * NR + r], cnt = a.req_u32[(size_t)CBH_RQ_ACT_CNT * NR + r];
+  for (u32 k = 0; k < cnt; ++k) {
+    const u32 w = a.packed ? a.packed[off + k] : 0u;
+    const u32 st = a.packed ? cbh_pk_status(w) : (u32)a.status[off + k];
+    const u32 now = ((f & 2u) || st == (u32)CBH_ST_UNSUPPORTED) ? (u32)CBH_ST_UNSUPPORTED : (u32)CBH_ST_CEL_ERROR;
+    if (a.packed) a.packed[off + k] = (w & ~(3u << 2)) | (now << 2); else if (a.status) a.status[off + k] = (u8)now;
+  }
+}
 // the packed results of a flat launch (CBH_FI_PACKED_RES, in the policy array) back into the wide form, before cbh_result_download
 // copies it
 struct PkUnpackArgs { CBH_G u8* effect; CBH_G u8* status; CBH_G u32* policy; CBH_G u32* scope; u32 n; u32 bits; };

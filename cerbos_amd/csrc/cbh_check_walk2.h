@@ -1061,11 +1061,44 @@ struct CbhPlan {
   bool walk_wide;                    // kind 2, batch with requests of five to eight roles: cbh_walk2_wide_kernel (+ its pre-pass) for those
   bool walk_awide;                   // kind 2, batch with requests of nine to sixteen actions: cbh_walk2_awide_kernel (+ its pre-pass) for those
   bool trail;                        // kind 2: the walks are the cbh_walk2_*trail_kernel forms (CBH_F_WANT_EFFECTIVE_POLICIES)
+  u32 groups;                        // kind 1: > 1 = the batch's requests have 5 .. 64 actions - `kernel`'s action-group instantiation, launched this often (flat_body AGROUP)
+  u32 each_from;                     // ... FlatGroupDev.each_from: from how many actions on the plan without groups hands a request to the general walk
 };
+// From how many groups on action groups are planned: every launch re-runs the prologue, and the walk's kernels, which decide a
+// request of up to 16 actions in one pass, are no slower on a flat table than they are anywhere.  profiles/flat_action_groups_ab.txt
+// (MI355X, 250 000 requests, decisions/s, min - max of five repetitions with groups against without; a shape is taken only where the
+// ranges lie apart):
+//   C2 (no derived roles)  G = 2 (all 8)   56.0 - 58.4 G against 55.5 - 58.6 G   no      G = 3 (all 12)  64.6 - 65.2 G against 38.8 - 39.3 G   yes
+//                          G = 4 (all 16)  58.2 - 59.8 G against 40.3 - 41.0 G   yes     G = 5, 10, 16 (1 .. 10 actions, 1 % at 20 / 40 / 64)  yes, 1.4 - 1.8 x
+//   C3 (derived roles)     G = 2, 3, 4 (all 8 / 12 / 16)   18.3 - 22.9 G against 23.7 - 30.6 G   no
+//                          G = 5, 10, 16 (1 % at 20 / 40 / 64: the general walk decides those requests without groups)   yes, 1.9 - 2.1 x
+// So: three groups for a table without derived roles, five - more than CBH_W2_AWIDE_NA actions - for one with; below, the plan without groups.
+// No upper bound: sixteen groups, CBH_MAX_ACTIONS_PER_REQUEST actions, are among the shapes measured.
+#define CBH_FLAT_MIN_GROUPS 3u
+#define CBH_FLAT_MIN_GROUPS_DR 5u
+// the group count a flat table's batch of this shape is planned with, 0 = not in groups (shared by cbh_plan and the host's tag scans)
+static inline u32 cbh_flat_action_groups(u32 n_derived_roles, u32 max_actions, u32 max_roles) {
+  const u32 g = (max_actions + 3u) / 4u;
+  return (max_roles <= 4 && max_actions > 4 && max_actions <= CBH_MAX_ACTIONS_PER_REQUEST && g >= (n_derived_roles ? CBH_FLAT_MIN_GROUPS_DR : CBH_FLAT_MIN_GROUPS)) ? g : 0u;
+}
 static inline CbhPlan cbh_plan(u32 table_flags, u32 n_derived_roles, bool has_globs, u32 gslots_generic, u32 gslots_all, u32 max_actions,
-                               u32 max_roles, bool plain_tags, u32 eval_flags, bool no_flat, bool no_walk2, u32 max_bucket, bool no_walk2_wide = false, bool masks = false) {
-  CbhPlan p; p.n_gwords = 0; p.n_gslots = 0; p.wide_kernel = nullptr; p.walk_wide = false; p.walk_awide = false; p.trail = false;
+                               u32 max_roles, bool plain_tags, u32 eval_flags, bool no_flat, bool no_walk2, u32 max_bucket, bool no_walk2_wide = false, bool masks = false,
+                               bool action_groups = false) {
+  CbhPlan p; p.n_gwords = 0; p.n_gslots = 0; p.wide_kernel = nullptr; p.walk_wide = false; p.walk_awide = false; p.trail = false; p.groups = 1; p.each_from = 0xFFFFFFFFu;
   bool flat = false;
+  // `action_groups` (the library's plan_for; NOT the kernel emulator, which launches a flat kernel once and so keeps the plan below as
+  // an independent reference): a flat table's batch of requests with 5 .. 64 actions and at most four roles is planned as its
+  // four-action sibling, launched once per four actions.  Not strict (no flat kernel is), not the trail, not a cycle-count launch,
+  // and not below the group counts at which the launches were measured faster than the plan without them (CBH_FLAT_MIN_GROUPS).
+  if (action_groups && !no_flat && (table_flags & CBH_MF_FLAT) && cbh_flat_action_groups(n_derived_roles, max_actions, max_roles) != 0 && !(eval_flags & (CBH_F_STRICT_EVALUATION | CBH_F_WANT_EFFECTIVE_POLICIES | CBH_F_DEBUG_CYCLES))) {
+    // (where the plan without groups marks a derived-role definition's error per action: its general walk's requests)
+    const CbhPlan off = cbh_plan(table_flags, n_derived_roles, has_globs, gslots_generic, gslots_all, max_actions, max_roles, plain_tags, eval_flags, no_flat, no_walk2, max_bucket, no_walk2_wide, masks);
+    p = cbh_plan(table_flags, n_derived_roles, has_globs, gslots_generic, gslots_all, 4u, max_roles, plain_tags, eval_flags, no_flat, no_walk2, max_bucket, no_walk2_wide, masks);
+    if (p.kind != 1 || !cbh_flat_group_variant(p.kernel)) return off;
+    p.groups = (max_actions + 3u) / 4u;
+    p.each_from = off.kind == 0 ? 0u : (off.kind == 2 && off.wide_kernel) ? ((off.walk_awide ? CBH_W2_AWIDE_NA : CBH_W2_NA) + 1u) : 0xFFFFFFFFu;
+    return p;
+  }
   // the effective policies of a call are what the reference's loops TOUCH, role by role in order (check.go:208-442, 302-304): the
   // general walk keeps that order; the flat kernels and cbh_walk2_kernel walk a request's roles side by side
   const bool want_ep = (eval_flags & CBH_F_WANT_EFFECTIVE_POLICIES) != 0;

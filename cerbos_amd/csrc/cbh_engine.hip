@@ -274,6 +274,7 @@ struct cbh_device_batch {
   // The batch has its compact form (cbh_vm.h BatchDev.creq / cval; batch_compact below): the flat kernels' compact instantiations read it.
   bool compact = false;
   u64* allow_bits = nullptr;   // cbh_result_download_allow_bits: the bitmap's device words, allocated at the first call
+  u8* dflag = nullptr;         // action-group launches on a table with derived roles (FlatGroupDev.dflag): [n_requests], allocated at the first such check
 };
 
 static void replica_destroy(Replica* r) {

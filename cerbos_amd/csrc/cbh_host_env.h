@@ -29,3 +29,6 @@ static inline int wire_lds_mode(int dflt_when_unset) {
 // CBH_FLAT_ANY (measurement / test aid): every batch counts as one with int or container tags - always the flat variant with
 // the evaluator call.  Read here for the three places that call a batch "plain" (host batches, cross products, wire batches).
 static inline bool flat_any_forced() { static const bool on = env_set("CBH_FLAT_ANY"); return on; }
+// CBH_FLAT_ACTION_GROUPS=0 (measurement aid, like CBH_NO_FLAT): a flat table's batches of requests with more than four actions keep the
+// plan they had before the flat kernels' action groups (cbh_check_walk2.h cbh_plan) - the walk's kernels and the general walk.
+static inline bool flat_action_groups_on() { static const bool on = env_int("CBH_FLAT_ACTION_GROUPS", 1) != 0; return on; }

@@ -105,7 +105,7 @@ extern "C" void cbh_result_bind_slab(cbh_result* r, void* slab, uint32_t n_tuple
 }
 
 struct Layout {
-  Seg args, req, roles, act, ctag, cval, htag, hval, soff, sbytes, sflags, gbits, gres, eff, pol, scope, status, edr;
+  Seg args, req, roles, act, ctag, cval, htag, hval, soff, sbytes, sflags, gbits, gres, dflag, eff, pol, scope, status, edr;
   size_t in_begin, in_end, out_begin, total;
 };
 static Layout make_layout(const cbh_batch* in, const cbh_table* t) {
@@ -127,6 +127,10 @@ static Layout make_layout(const cbh_batch* in, const cbh_table* t) {
   // results of the evaluation sites (cbh_walk2_pre_kernel -> cbh_walk2_kernel), sized for a batch that needs all of them
   const size_t gw = (t->meta[CBH_M_FLAGS] & CBH_MF_WALK2) ? w2_gwords(t->meta[CBH_M_GSLOTS_GENERIC], t->meta[CBH_M_GSLOTS_ALL], false) : 0;
   L.gres = Seg{cur, gw * NR * 8, nullptr}; cur += (L.gres.bytes + 255) & ~(size_t)255;
+  // a byte per request for the flat kernels' action groups on a table with derived roles (FlatGroupDev.dflag).  Whatever the
+  // batch's action counts: the layout is fixed before the O(n_requests) scan that finds them (cbh_check_batch starts a slab's upload first).
+  const bool groups = (t->meta[CBH_M_FLAGS] & CBH_MF_FLAT) && !t->reps.empty() && t->reps[0]->dev.n_dr && flat_action_groups_on();
+  L.dflag = Seg{cur, groups ? NR : 0, nullptr}; cur += (L.dflag.bytes + 255) & ~(size_t)255;
   L.out_begin = cur;
   const OutOffsets oo = out_offsets(NT, NR);
   L.eff = Seg{cur + oo.eff, NT, nullptr}; L.status = Seg{cur + oo.status, NT, nullptr}; L.pol = Seg{cur + oo.pol, NT * 4, nullptr};
@@ -167,9 +171,9 @@ static void launch_resolve(const Replica* rep, const KernelArgs& ka, const Layou
     hipLaunchKernelGGL(cbh_resolve_globs_kernel, dim3(grid), dim3(CBH_BLOCK), (size_t)(2 + 512) * maxw * sizeof(u64), s, rep->dev, ka.b);
   } else if (hipMemsetAsync(ka.b.gbits, 0, L.gbits.bytes, s) != hipSuccess) rc = -1;   // no automata: no string matches a glob
 }
-static void launch_check(const Replica* rep, KernelArgs ka, const KernelArgs* d_args, u32 lo, u32 hi, const BatchShape& sh, hipStream_t s) {
+static void launch_check(const Replica* rep, KernelArgs ka, const KernelArgs* d_args, u32 lo, u32 hi, const BatchShape& sh, hipStream_t s, u8* dflag) {
   if (hi <= lo) return;
-  launch_plan(plan_for(rep->dev, sh.max_actions, sh.max_roles, sh.plain_tags(), ka.flags), rep->dev, ka, d_args, lo, hi, sh.wide_lo, sh.wide_hi, 0, s);
+  launch_plan(plan_for(rep->dev, sh.max_actions, sh.max_roles, sh.plain_tags(), ka.flags), rep->dev, ka, d_args, lo, hi, sh.wide_lo, sh.wide_hi, 0, s, nullptr, nullptr, dflag);
 }
 
 // a small batch on one device: everything packed into the pinned staging block.  Two ways across PCIe:
@@ -203,7 +207,7 @@ static int run_small(cbh_table* t, Replica* rep, const cbh_batch* in, const cbh_
     HIPCHK(hipMemcpyAsync(c->d, c->h, L.in_end, hipMemcpyHostToDevice, s));
     launch_resolve(rep, ka, L, s, rc);
   }
-  launch_check(rep, ka, (const KernelArgs*)(base + L.args.off), 0, in->n_requests, sh, s);
+  launch_check(rep, ka, (const KernelArgs*)(base + L.args.off), 0, in->n_requests, sh, s, L.dflag.bytes ? base + L.dflag.off : nullptr);
   HIPCHK(hipGetLastError());
   if (rc != 0) return fail("hipMemsetAsync failed");
   if (!zero_copy && L.total > L.out_begin) HIPCHK(hipMemcpyAsync(c->h + L.out_begin, c->d + L.out_begin, L.total - L.out_begin, hipMemcpyDeviceToHost, s));
@@ -279,7 +283,7 @@ static int run_range(cbh_table* t, Replica* rep, const cbh_batch* in, const cbh_
     if (!pre && slab_upload(c, rep, L, slab, NR) != 0) return -1;
     launch_resolve(rep, ka, L, s0, rc);
     if (rc != 0) return fail("hipMemsetAsync failed");
-    launch_check(rep, ka, d_args, 0, (u32)NR, sh, s0);
+    launch_check(rep, ka, d_args, 0, (u32)NR, sh, s0, L.dflag.bytes ? base + L.dflag.off : nullptr);
     HIPCHK(hipGetLastError());
     struct Run { size_t off, bytes; uint8_t* dst; };
     Run run{0, 0, nullptr};
@@ -335,7 +339,7 @@ static int run_range(cbh_table* t, Replica* rep, const cbh_batch* in, const cbh_
     size_t tb = 0, te = 0;
     if (hi > lo) tuples_of(lo, hi, tb, te);
     if (te > tb) HIPCHK(hipMemcpyAsync(base + L.act.off + tb * 4, in->tuple_action + tb, (te - tb) * 4, hipMemcpyHostToDevice, s));
-    launch_check(rep, ka, d_args, lo, hi, sh, s);
+    launch_check(rep, ka, d_args, lo, hi, sh, s, L.dflag.bytes ? base + L.dflag.off : nullptr);
     HIPCHK(hipGetLastError());
     if (te > tb) {
       HIPCHK(hipMemcpyAsync(out->effect + tb, base + L.eff.off + tb, te - tb, hipMemcpyDeviceToHost, s));
@@ -363,7 +367,7 @@ static int run_range(cbh_table* t, Replica* rep, const cbh_batch* in, const cbh_
     size_t tb = 0, te = 0;
     tuples_of(a, b, tb, te);
     if (te > tb) HIPCHK(hipMemcpyAsync(base + L.act.off + tb * 4, in->tuple_action + tb, (te - tb) * 4, hipMemcpyHostToDevice, s));
-    launch_check(rep, ka, d_args, a, b, sh, s);
+    launch_check(rep, ka, d_args, a, b, sh, s, L.dflag.bytes ? base + L.dflag.off : nullptr);
     if (te > tb) {
       HIPCHK(hipMemcpyAsync(out->effect + tb, base + L.eff.off + tb, te - tb, hipMemcpyDeviceToHost, s));
       if (out->policy) HIPCHK(hipMemcpyAsync(out->policy + tb, base + L.pol.off + tb * 4, (te - tb) * 4, hipMemcpyDeviceToHost, s));

@@ -3,6 +3,10 @@
 // the downloads, the audit trail.
 #pragma once
 
+// Would cbh_plan decide a batch of this shape in action groups (flags permitting)?  Then the tags select its kernel, as for four actions.
+static bool flat_groups_shape(const cbh_table* t, u32 max_actions, u32 max_roles) {
+  return flat_action_groups_on() && !t->reps.empty() && cbh_flat_action_groups(t->reps[0]->dev.n_dr, max_actions, max_roles) != 0;
+}
 // ---- batch validation (O(n_requests), both entry points) ---------------------------------------------------
 // Offsets and counts the kernels index device memory with must lie inside the arrays they index.  String ids
 // need no host pass: the kernels only compare them, or bound them before using one as an index.
@@ -77,7 +81,8 @@ static int validate_batch(const cbh_table* t, const cbh_batch* in, BatchShape& s
   sh.max_actions = maxa; sh.max_roles = maxr; sh.ascending = !unordered;
   sh.wide_lo = whi ? wlo : 0; sh.wide_hi = whi;
   sh.tags = nullptr; sh.n_tags = 0; sh.plain.store(-1, std::memory_order_relaxed);
-  if (((t->meta[CBH_M_FLAGS] & CBH_MF_FLAT) && maxa <= 4 && maxr <= 4) ||
+  // (a flat kernel decides the batch: four actions or, in the action groups cbh_plan takes, up to CBH_MAX_ACTIONS_PER_REQUEST)
+  if (((t->meta[CBH_M_FLAGS] & CBH_MF_FLAT) && maxr <= 4 && (maxa <= 4 || flat_groups_shape(t, maxa, maxr))) ||
       ((t->meta[CBH_M_FLAGS] & CBH_MF_WALK2) && t->meta[CBH_M_GSLOTS_ALL] > t->meta[CBH_M_GSLOTS_GENERIC])) { sh.tags = in->col_tag; sh.n_tags = (size_t)in->n_columns * NR; }
   sh.sens_cols = t->meta[CBH_M_SENS_COLS]; sh.n_req = NR;
   if (in->n_columns < 32) sh.sens_cols &= (1u << in->n_columns) - 1u;
@@ -247,7 +252,7 @@ static int cross_validate(cbh_table* t, uint32_t device_index, const cbh_batch* 
   bool plain = true;
   {
     const u32 mf = t->meta[CBH_M_FLAGS];
-    const bool matters = ((mf & CBH_MF_FLAT) && (cs.plan_a ? cs.plan_a : A) <= 4 && (maxr <= 4 || cs.group_roles)) || ((mf & CBH_MF_WALK2) && t->meta[CBH_M_GSLOTS_ALL] > t->meta[CBH_M_GSLOTS_GENERIC]);
+    const bool matters = ((mf & CBH_MF_FLAT) && ((cs.plan_a ? cs.plan_a : A) <= 4 || flat_groups_shape(t, (u32)A, maxr)) && (maxr <= 4 || cs.group_roles)) || ((mf & CBH_MF_WALK2) && t->meta[CBH_M_GSLOTS_ALL] > t->meta[CBH_M_GSLOTS_GENERIC]);
     u32 sens = t->meta[CBH_M_SENS_COLS];
     if (ncol < 32) sens &= (1u << ncol) - 1u;
     bool hit = false;
@@ -331,13 +336,14 @@ static void collect_times(Replica* r) {   // after the stream has been synchroni
 }
 
 // CBH_NO_FLAT=1 / CBH_NO_WALK2=1 / CBH_NO_WALK2_WIDE=1 (measurement aids): leave the flat kernels / cbh_walk2_kernel out of the choice
-static CbhPlan plan_for(const TableDev& dev, u32 max_actions, u32 max_roles, bool plain_tags, u32 eval_flags) {
+// `action_groups` = false: the plan as it is without the flat kernels' action groups (what CBH_FLAT_ACTION_GROUPS=0 gives everywhere)
+static CbhPlan plan_for(const TableDev& dev, u32 max_actions, u32 max_roles, bool plain_tags, u32 eval_flags, bool action_groups = true) {
   static const bool no_flat = env_set("CBH_NO_FLAT"), no_walk2 = env_set("CBH_NO_WALK2");
   static const bool no_walk2_wide = env_set("CBH_NO_WALK2_WIDE");   // (measurement aid: requests with five to eight roles on the general walk, as before the wider shape)
   const bool has_globs = (dev.nfa_words[0] | dev.nfa_words[1] | dev.nfa_words[2]) != 0 || (dev.flags & CBH_MF_HAS_ANY_PATTERN);
   static const bool force_staged = env_set("CBH_FORCE_STAGED");   // (tests: the staged record walk on tables of any size)
   return cbh_plan(dev.flags, dev.n_dr, has_globs, dev.gslots_generic, dev.gslots_all, max_actions, max_roles, plain_tags, eval_flags, no_flat, no_walk2,
-                  force_staged ? 0xFFFFFFFFu : dev.max_bucket, no_walk2_wide, cbh_flat_use_masks(dev.segs, dev.max_bucket));
+                  force_staged ? 0xFFFFFFFFu : dev.max_bucket, no_walk2_wide, cbh_flat_use_masks(dev.segs, dev.max_bucket), action_groups && flat_action_groups_on());
 }
 // (on by default since round 5: C5 11.8 -> 12.4 G decisions/s, C5W 7.61 -> 7.67, profiles/r05_presplit_ab.txt; CBH_PRE_SPLIT=0: the fused pre-pass)
 static bool pre_split_on() { static const bool on = env_int("CBH_PRE_SPLIT", 1) != 0; return on; }
@@ -365,7 +371,7 @@ static bool packed_tags_pay(cbh_check_kernel_fn fn, u32 threads, size_t lds_wide
 // the launches that decide the requests [lo, hi) of `ka.b`; [wide_lo, wide_hi) = where the batch's requests wider than
 // cbh_walk2_kernel's shape lie (empty: none)
 static void launch_plan(const CbhPlan& pl, const TableDev& dev, KernelArgs ka, const KernelArgs* d_args, u32 lo, u32 hi, u32 wide_lo, u32 wide_hi,
-                        size_t pad, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr) {
+                        size_t pad, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr, u8* dflag = nullptr) {
   if (hi <= lo) return;
   ka.b.req_lo = lo; ka.b.req_hi = hi;
   ka.flags &= ~(u32)(CBH_FI_MASK & ~(CBH_FI_PACKED_RES | CBH_FI_COMPACT));   // (the result form and the input form are the caller's choice: cbh_check_resident)
@@ -419,6 +425,37 @@ static void launch_plan(const CbhPlan& pl, const TableDev& dev, KernelArgs ka, c
   }
   static const bool pre_only = env_set("CBH_PRE_ONLY");   // measurement aid (profiling build): the pre-pass alone
   if (pre_only && pl.kind == 2) return;
+  if (pl.kind == 1 && pl.groups > 1) {
+    // ---- action groups (cbh_check_flat.h flat_body AGROUP): the plan's kernel once per four actions, in order, same grid, range and LDS.
+    // `dflag` ([n_requests] bytes of the batch, a table with derived roles whose call wants them): cleared for the range, ORed into
+    // by the groups, read by the status kernel behind the last one.
+    const cbh_group_kernel_fn gfn = cbh_flat_group_variant(pl.kernel);
+    const auto lds_of = plan_lds(false, CBH_W2_NA, pad);
+    const size_t wide = lds_of(false), packed = lds_of(true);
+    const bool use_packed = packed_tags_pay(reinterpret_cast<cbh_check_kernel_fn>(gfn), pl.threads, wide, packed);
+    KernelArgs a = ka;
+    if (use_packed) a.flags |= CBH_FI_PACKED_TAGS;
+    FlatGroupDev ag{};
+    ag.dflag = (dev.n_dr && (ka.flags & CBH_F_WANT_DERIVED_ROLES) && ((ka.flags & CBH_FI_PACKED_RES) || ka.o.status)) ? dflag : nullptr;
+    ag.each_from = pl.each_from;
+    if (ag.dflag) (void)hipMemsetAsync(ag.dflag + lo, 0, n, s);
+    const dim3 grid((n + pl.threads - 1) / pl.threads), block(pl.threads);
+    if (trace_on()) std::fprintf(stderr, "[cbh] action groups=%u requests [%u,%u) status kernel=%d\n", pl.groups, lo, hi, ag.dflag ? 1 : 0);
+    for (u32 g = 0; g < pl.groups; ++g) {
+      ag.group = g;
+      const bool last = g + 1 == pl.groups && !ag.dflag;
+      if (ev0 || (ev1 && last)) { hipExtLaunchKernelGGL(gfn, grid, block, use_packed ? packed : wide, s, ev0, last ? ev1 : nullptr, 0, a, d_args, ag); ev0 = nullptr; }
+      else hipLaunchKernelGGL(gfn, grid, block, use_packed ? packed : wide, s, a, d_args, ag);
+    }
+    if (ag.dflag) {
+      FlatGroupStatusArgs sa{};
+      sa.req_u32 = ka.b.req_u32; sa.dflag = ag.dflag; sa.n_requests = ka.b.n_requests; sa.lo = lo; sa.hi = hi;
+      if (ka.flags & CBH_FI_PACKED_RES) sa.packed = ka.o.policy; else sa.status = ka.o.status;
+      if (ev1) hipExtLaunchKernelGGL(cbh_flat_group_status_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, nullptr, ev1, 0, sa);
+      else hipLaunchKernelGGL(cbh_flat_group_status_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, sa);
+    }
+    return;
+  }
   go((ka.flags & CBH_FI_COMPACT) ? cbh_flat_compact_variant(pl.kernel) : pl.kernel, (n + pl.threads - 1) / pl.threads, pl.threads, plan_lds(false, CBH_W2_NA, pad), ka, true);
 }
 // CBH_LDS_PAD=<bytes> (measurement aid): extra dynamic LDS per workgroup of the resident launches, to hold the occupancy down
@@ -444,7 +481,7 @@ static bool launch_is_compact(const cbh_device_batch* b, const CbhPlan& pl, u32 
 #ifdef CBH_PROFILE_CYCLES
   eval_flags &= ~(u32)CBH_F_DEBUG_CYCLES;
 #endif
-  return b->compact && pl.kind == 1 && !(eval_flags & CBH_F_DEBUG_CYCLES) && cbh_flat_compact_variant(pl.kernel) != nullptr;
+  return b->compact && pl.kind == 1 && pl.groups <= 1 && !(eval_flags & CBH_F_DEBUG_CYCLES) && cbh_flat_compact_variant(pl.kernel) != nullptr;
 }
 
 extern "C" int cbh_check_resident(cbh_table* t, cbh_device_batch* b, const cbh_params* p) {
@@ -478,6 +515,8 @@ extern "C" int cbh_check_resident(cbh_table* t, cbh_device_batch* b, const cbh_p
   const CbhPlan pl = d.n_requests ? plan_for(rep->dev, b->max_actions, b->max_roles, b->plain_tags, p->flags) : CbhPlan{};
   // A flat launch writes its results packed, a word per tuple, where the table's ids fit (not: the trail's kernels, the wire road's
   // batches - cbh_wire_outputs reads the wide arrays -, cycle-count launches); and for a table without derived roles no mask at all.
+  // (action groups on a table with derived roles: a byte per request for the error of a definition, flat_body AGROUP)
+  if (pl.kind == 1 && pl.groups > 1 && rep->dev.n_dr && !b->dflag && dalloc(b, b->dflag, (size_t)d.n_requests) != 0) { b->dflag = nullptr; return -1; }
   b->res_packed = pl.kind == 1 && !cbh_is_flat_trail_kernel(pl.kernel) && !b->wire && !(p->flags & CBH_F_DEBUG_CYCLES) && pk_fits(rep->dev);
   b->edr_zero = b->res_packed && rep->dev.n_dr == 0;
   {
@@ -506,7 +545,7 @@ extern "C" int cbh_check_resident(cbh_table* t, cbh_device_batch* b, const cbh_p
   }
   sl.pending = false;
   if (d.n_requests) {
-    launch_plan(pl, rep->dev, b->last_args, (const KernelArgs*)b->d_args, 0, d.n_requests, b->wide_lo, b->wide_hi, lds_pad(), s, timed ? sl.ev[2] : nullptr, timed ? sl.ev[3] : nullptr);
+    launch_plan(pl, rep->dev, b->last_args, (const KernelArgs*)b->d_args, 0, d.n_requests, b->wide_lo, b->wide_hi, lds_pad(), s, timed ? sl.ev[2] : nullptr, timed ? sl.ev[3] : nullptr, b->dflag);
     sl.pending = timed;
   }
   HIPCHK(hipGetLastError());
@@ -546,6 +585,7 @@ extern "C" const char* cbh_plan_describe(cbh_table* t, cbh_device_batch* b, cons
                            : pl.kernel == cbh_check_flat_kernel_staged ? "cbh_check_flat_kernel_staged" : pl.kernel == cbh_check_flat_kernel_masks ? "cbh_check_flat_kernel_masks"
                            : pl.kernel == cbh_check_flat_kernel_any_masks ? "cbh_check_flat_kernel_any_masks" : "cbh_check_flat_kernel_any_staged";
   else s = "cbh_check_kernel*";
+  if (pl.kind == 1 && pl.groups > 1) { char m[32]; snprintf(m, sizeof m, ", %u action groups", pl.groups); s += m; }
   if (launch_is_compact(b, pl, p->flags)) { char m[64]; snprintf(m, sizeof m, "[compact inputs, narrow columns 0x%x]", b->dev.compact_info & CBH_CI_NARROW_MASK); s += m; }
   return s.c_str();
 }
@@ -669,7 +709,7 @@ static u32 cross_role_groups(const cbh_cross_set* cs) { return cs->maxr > 4u ? (
 // requests would be decided by the general walk, by the product's own plan (launch_plan: CBH_FI_ONLY_WIDE / CBH_FI_ONLY_WIDER).
 // (The flags that change a product's plan - strict evaluation, the trail - have no direct form: the plan under flags 0 is the one.)
 static u32 cross_open_from(const TableDev& dev, const cbh_cross_set* cs) {
-  const CbhPlan pp = plan_for(dev, cs->a, cs->maxr, cs->plain, 0);
+  const CbhPlan pp = plan_for(dev, cs->a, cs->maxr, cs->plain, 0, false);   // (the marks' places are those of the plan without action groups, which the groups reproduce)
   if (pp.kind == 0) return 0u;
   if (pp.kind != 2 || !pp.wide_kernel) return 0xFFFFFFFFu;
   if (pp.walk_wide || pp.walk_awide) return cs->a > CBH_W2_AWIDE_NA ? 0u : cs->a > CBH_W2_NA ? CBH_W2_NR + 1u : CBH_W2_WIDE_NR + 1u;   // cbh_is_wider

@@ -239,7 +239,17 @@ int cbh_check_batch(cbh_table* t, const cbh_batch* in, const cbh_params* p, cbh_
 int cbh_batch_upload(cbh_table* t, const cbh_batch* in, cbh_device_batch** out);
 int cbh_batch_upload_on(cbh_table* t, uint32_t device_index, const cbh_batch* in, cbh_device_batch** out);
 void cbh_batch_release(cbh_device_batch* b);
-/* Launches the kernels on the library's stream and returns without synchronising. */
+/* Launches the kernels on the library's stream and returns without synchronising.
+ * Which batches a flat table's kernels decide (cbh_check_resident and cbh_check_batch alike; a flat table holds resource policies
+ * whose records class masks decide): those whose requests all have at most four roles and at most CBH_MAX_ACTIONS_PER_REQUEST
+ * actions, unless the call is strict.  Up to four actions: one launch.  More: the same kernel once per four actions, G = (max
+ * actions + 3) / 4 launches in order on the batch's stream - "action groups", which cbh_plan_describe names (", G action groups").
+ * Results are bit for bit those of the plan without them (the walk's kernels and the general walk).  That plan still decides: the
+ * batches below the group counts at which the launches were measured faster - G < 3, i.e. up to eight actions, on any table; G < 5,
+ * up to sixteen actions, on a table with derived roles -, calls with the trail's flag, cycle-count launches,
+ * every batch with a principal of more than four roles, and everything under CBH_FLAT_ACTION_GROUPS=0 in the environment (a
+ * measurement aid). */
+#define CBH_HAS_FLAT_ACTION_GROUPS 1
 int cbh_check_resident(cbh_table* t, cbh_device_batch* b, const cbh_params* p);
 /* cbh_check_resident for bs[0 .. n) in order, in one call. */
 int cbh_check_resident_many(cbh_table* t, cbh_device_batch* const* bs, uint32_t n, const cbh_params* p);

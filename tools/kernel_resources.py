@@ -2,7 +2,8 @@
 """hipcc -Rpass-analysis=kernel-resource-usage remarks (stderr of a build) -> one line per kernel.
 usage: hipcc ... -Rpass-analysis=kernel-resource-usage 2> res.txt; python tools/kernel_resources.py res.txt [filter]
 (filter: a substring of the kernels' names - `_x` for the direct cross instantiations, cbh_check_flat_kernel_dr_x among them, `cbh_cross_` for
-the cross road's small kernels)"""
+the cross road's small kernels, `_g` with `cbh_flat_group` for the flat kernels' action-group instantiations cbh_check_flat_kernel_g, _dr_g, _any_g,
+_staged_g, _any_staged_g, _masks_g, _any_masks_g and cbh_flat_group_status_kernel)"""
 import re
 import sys
 
