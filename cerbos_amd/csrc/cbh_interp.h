@@ -62,6 +62,9 @@ __device__ __forceinline__ u64 wave_readlane64(u64 v, u32 lane) {
 // iteration-slot state word (per lane): bits 0..7 kind, bit 8 saw-error, bit 9 decided
 // (short-circuit value reached), bit 10 lane-live-at-entry, bit 11 iterating (not exhausted /
 // decided), bit 30 container is a map, bit 31 the macro itself is an error; bits 16..29 count.
+// The count never reaches bit 30: filter / map count the elements they kept, at most the CBH_ARENA_ENTRIES (48) reserved at
+// OP_ITER_BEGIN; exists_one counts its hits only as far as 2, since "exactly one" is all it is asked (a count of every hit
+// carried into ITS_MAP at the 16 384th, read 16 385 hits as one and took the list for a map from then on).
 #define ITS_ERRSEEN 0x100u
 #define ITS_DECIDED 0x200u
 #define ITS_ENTRY_LIVE 0x400u
@@ -559,6 +562,9 @@ __device__ __forceinline__ u32 run_uniform_impl(const KernelArgs* ka, const VmLd
         const u64 cont = c.it_cont[a * CBH_BLOCK + c.tid];
         const u32 iw = c.it_idx[a * CBH_BLOCK + c.tid], i = iw & 0xFFFFFu;
         u32 st = c.it_state[a * CBH_BLOCK + c.tid];
+        // (i < 0xFFFFF never ends a range early without a flag: a turn is OP_ITER_NEXT, at least one operation of the body - every
+        // macro's body pushes a value - and OP_ITER_ACC, three steps or more, so the 1 000 000 steps of this call are spent, and the
+        // wave's tuples flagged, before turn 333 334 - long before the 20-bit index is full)
         bool more = (st & ITS_RUNNING) && i < cont_len(cont) && i < 0xFFFFFu;
         // what the previous turn of the body built is dead now - unless the body's value IS what it built (map)
         if ((st & ITS_RUNNING) && (st & 0xFF) != IT_MAP && (st & 0xFF) != IT_MAP_FILTER) ap = (iw >> 20) & 63u;
@@ -621,7 +627,7 @@ __device__ __forceinline__ u32 run_uniform_impl(const KernelArgs* ka, const VmLd
             else st |= ITS_ERRSEEN;                                               // may be absorbed
           } else if (kind == IT_ALL) { if (!x.v) { st |= ITS_DECIDED; st &= ~ITS_RUNNING; } }
           else if (kind == IT_EXISTS) { if (x.v) { st |= ITS_DECIDED; st &= ~ITS_RUNNING; } }
-          else if (x.v) st += 0x10000u;
+          else if (x.v && !(st & 0x20000u)) st += 0x10000u;   // exists_one: 0, 1, "two or more" - the count stops at 2 (see ITS_MAP)
           c.it_state[a * CBH_BLOCK + c.tid] = st;
         }
         pc = loop_pc;
