@@ -448,7 +448,7 @@ __device__ __forceinline__ u64 load_u64g(const CBH_G u32* p) {   // 8-byte align
 // principal's record, kind, version and scope from the resource's, the actions from the launch (the same for every lane), the
 // columns from either row by their side (cc_fill_cross).  The walk and the fold are the same; no result word is written - one
 // ballot per action (and one of "status is not OK", where wanted) is stored by the wave's first lane.
-// A set whose principals have five to sixteen roles is decided four roles at a time (CrossRoleGroup.role_group, cbh_host_resident.h
+// A set whose principals have five to sixteen roles is decided four roles at a time (CrossRoleGroup.role_group, cbh_host_cross.h
 // cross_set_check): the launch of group g >= 1 takes the lanes' roles from the group's role words, leaves out the walks of the actions
 // an earlier group allowed and ORs its ballots into the planes.  For the two bits this is the reference's role loop unrolled: an
 // action is allowed iff some role allows it; an evaluation counts iff no earlier role allowed the action - within a group the fold's
@@ -1537,7 +1537,7 @@ static inline bool cbh_is_flat_compact_kernel(cbh_check_kernel_fn fn) {
 }
 // The direct cross road's instantiations (flat_body CROSS; cerbos_hip.h cbh_cross_check): MODE 0, 1, 2 without the evaluator call, the
 // cross arguments a by-value parameter of their own.  Same attributes as their compact siblings.  A set of more than four actions is
-// decided by several launches of the same kernel, four actions each (cbh_host_resident.h cross_set_check): nothing here knows.  So is a
+// decided by several launches of the same kernel, four actions each (cbh_host_cross.h cross_set_check): nothing here knows.  So is a
 // set of principals with more than four roles, four roles each: CrossRoleGroup.role_group.
 __global__ CBH_FLAT_ATTRS(7) void cbh_check_flat_kernel_x(const KernelArgs a, const KernelArgs* __restrict__ ka, const CrossDev x) {
   CBH_FLAT_CTX_C(a, ka);

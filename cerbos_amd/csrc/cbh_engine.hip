@@ -20,8 +20,8 @@
 //     devices, each range pipelined in chunks over three streams (upload / kernels / download overlap);
 //   * tables are reference counted, so a released table drains its in-flight batches (manager.go:86-124).
 // This file is the core - errors, the engine, a table and its replicas, a resident batch and the pool its buffers come from -
-// and includes the roads, host-only headers, at its end: cbh_host_resident.h, cbh_host_wire.h, cbh_host_oneshot.h (and
-// cbh_host_env.h, how the CBH_* variables are read, in front of everything).  One translation unit, as before.
+// and includes the roads, host-only headers, at its end: cbh_host_resident.h, cbh_host_cross.h, cbh_host_wire.h, cbh_host_oneshot.h
+// (and cbh_host_env.h, how the CBH_* variables are read, in front of everything).  One translation unit, as before.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <dlfcn.h>
@@ -37,6 +37,7 @@
 #include <cstring>
 #include <ctime>
 #include <condition_variable>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
@@ -252,6 +253,15 @@ struct WireBatch {
   u32* sizes = nullptr; u64* wavesum = nullptr; u64* waveoff = nullptr; WireOutStats* ostats = nullptr; u64* out_off = nullptr; u8* out_flags = nullptr;
 };
 
+// What of a batch's requests selects its kernels (plan_for) and places their launches (launch_plan).  Every maker of a resident batch
+// works it out for its own source - BatchShape::shape (host arrays), cross_validate (halves), cross_pairs_upload (pairs of a set),
+// wf_finish (the flattener's statistics) - and assigns it once.
+struct PlanShape {
+  u32 max_actions = 0, max_roles = 0;   // largest CBH_RQ_ACT_CNT / ROLE_CNT of the batch
+  u32 wide_lo = 0, wide_hi = 0;         // the requests with more than CBH_W2_NA actions or CBH_W2_NR roles lie in [wide_lo, wide_hi)
+  bool plain_tags = false;              // BatchShape::plain_tags
+};
+
 struct cbh_device_batch {
   cbh_table* table = nullptr;
   Replica* rep = nullptr;
@@ -261,9 +271,7 @@ struct cbh_device_batch {
   KernelArgs* d_args = nullptr;   // device copy of the launch arguments
   KernelArgs last_args;           // what d_args currently holds
   bool have_args = false;
-  u32 max_actions = 0, max_roles = 0;   // largest CBH_RQ_ACT_CNT / ROLE_CNT of the batch: select the kernel
-  u32 wide_lo = 0, wide_hi = 0;         // BatchShape::wide_lo / wide_hi
-  bool plain_tags = false;              // BatchShape::plain_tags
+  PlanShape shape;
   std::vector<std::pair<void*, size_t>> allocs;   // (block, capacity) taken from the replica's pool
   bool wire = false;   // a batch the device flattened (cbh_wire_flatten): `w` is in use
   WireBatch w;
@@ -510,6 +518,7 @@ static int dalloc(cbh_device_batch* b, T*& dst, size_t n) {
 }
 
 #include "cbh_host_resident.h"   // batches that stay on the device: upload, plan, launch, download, trail
+#include "cbh_host_cross.h"      // N x M x A from N + M halves: the materialised product, the direct set, its pairs
 #include "cbh_host_wire.h"       // serialized messages in, serialized answers out: the device flattener and assembler
 #include "cbh_host_oneshot.h"    // cbh_check_batch / cbh_trace_batch: a host batch, one round trip
 #endif  // !__HIP_DEVICE_COMPILE__

@@ -1,4 +1,4 @@
-// Host side of libcerbos_hip.so, part 1 of 4 (cbh_engine.hip includes them in order): how the library reads a CBH_* variable.
+// Host side of libcerbos_hip.so, part 1 of 5 (cbh_engine.hip includes them in order): how the library reads a CBH_* variable.
 // A few helpers, no cache of their own: a call site that wants the value read once keeps it in a `static const`, as every site
 // but CBH_CHUNK_REQUESTS and CBH_BCAST does.  The conventions differ from knob to knob and are kept as they grew (the table in
 // DESIGN.md lists every variable with its own): "set at all" (env_set), "first character is c" (env_is), "is exactly this word" (env_eq), atoi / atol with a

@@ -1,4 +1,4 @@
-// Host side of libcerbos_hip.so, part 4 of 4 (included by cbh_engine.hip, host pass only): the one-shot path.
+// Host side of libcerbos_hip.so, part 5 of 5 (included by cbh_engine.hip, host pass only): the one-shot path.
 #pragma once
 
 // ---- one-shot path: CheckResources round trip for a host batch ------------------------------------------

@@ -1,46 +1,70 @@
-// Host side of libcerbos_hip.so, part 2 of 4 (included by cbh_engine.hip, host pass only): resident batches - validation, the
-// three makers (host arrays, cross product; the wire road's is in cbh_host_wire.h), the choice of kernels and their launches,
-// the downloads, the audit trail.
+// Host side of libcerbos_hip.so, part 2 of 5 (included by cbh_engine.hip, host pass only): resident batches - validation, the
+// maker from host arrays and what every maker shares (the cross road's are in cbh_host_cross.h, the wire road's in cbh_host_wire.h),
+// the choice of kernels and their launches, the downloads, the audit trail.
 #pragma once
 
 // Would cbh_plan decide a batch of this shape in action groups (flags permitting)?  Then the tags select its kernel, as for four actions.
 static bool flat_groups_shape(const cbh_table* t, u32 max_actions, u32 max_roles) {
   return flat_action_groups_on() && !t->reps.empty() && cbh_flat_action_groups(t->reps[0]->dev.n_dr, max_actions, max_roles) != 0;
 }
+// ---- plain tags: do the attribute columns hold plain scalars only - no int / uint (cross-type numerics) and no list / map (deep
+// equality)?  Then no classified leaf can need the shared evaluator and the flat kernel without that call decides the batch
+// (cbh_check_flat.h).  The answer costs a pass over tag bytes, so it is asked only where it can select a kernel, for the counts the
+// plan is made for - a batch's largest ones; for a direct set (cbh_host_cross.h) min(A, 4) and, with role groups, min(max_roles, 4):
+//   CBH_MF_FLAT   max_roles <= 4 and (max_actions <= 4 or flat_groups_shape)   yes: a flat kernel decides the batch, at once or in action groups
+//   CBH_MF_WALK2  GSLOTS_ALL > GSLOTS_GENERIC, whatever the shape              yes: the answer sizes the walk's evaluation sites
+//   neither line holds (a flat table's other shapes among them)                no: the walk's or the general kernels, no site that depends on it
+static bool plain_tags_select(const cbh_table* t, u32 max_actions, u32 max_roles) {
+  const u32 mf = t->meta[CBH_M_FLAGS];
+  return ((mf & CBH_MF_FLAT) && max_roles <= 4 && (max_actions <= 4 || flat_groups_shape(t, max_actions, max_roles))) ||
+         ((mf & CBH_MF_WALK2) && t->meta[CBH_M_GSLOTS_ALL] > t->meta[CBH_M_GSLOTS_GENERIC]);
+}
+// tags 2, 3 (int, uint) and 6, 7 (list, map) are exactly the bytes x with (x & 0xFA) == 0x02: eight at a time
+static bool has_int_or_container_tag(const uint8_t* p, size_t n) {
+  size_t i = 0; uint64_t hit = 0;
+  for (; i + 8 <= n; i += 8) {
+    uint64_t w; std::memcpy(&w, p + i, 8);
+    const uint64_t z = (w & 0xFAFAFAFAFAFAFAFAull) ^ 0x0202020202020202ull;              // a zero byte where a tag matched
+    hit |= (z - 0x0101010101010101ull) & ~z & 0x8080808080808080ull;
+  }
+  for (; i < n; ++i) hit |= (uint64_t)((p[i] & 0xFAu) == 0x02u);
+  return hit != 0;
+}
+// The scan: does a column that can send a classified leaf to the evaluator (CBH_M_SENS_COLS, bit c) hold such a tag in a row that
+// counts?  `tags`: [n_columns][n_rows]; `rows(c)`: which rows of column c some request of the batch reads -
+//   a host batch: the whole column;
+//   halves, N principals then M resources: rows [0, N) of a principal-side column, rows [N, N + M) of a resource-side one - what a column's other rows hold is in no request of the product.
+struct TagRows { size_t first, count; };
+template <typename Rows>
+static bool sens_tag_hit(const cbh_table* t, const uint8_t* tags, u32 n_columns, size_t n_rows, Rows rows) {
+  for (u32 c = 0; c < 32 && c < n_columns; ++c) if ((t->meta[CBH_M_SENS_COLS] >> c) & 1u) {
+    const TagRows r = rows(c);
+    if (has_int_or_container_tag(tags + (size_t)c * n_rows + r.first, r.count)) return true;
+  }
+  return false;
+}
+
 // ---- batch validation (O(n_requests), both entry points) ---------------------------------------------------
 // Offsets and counts the kernels index device memory with must lie inside the arrays they index.  String ids
 // need no host pass: the kernels only compare them, or bound them before using one as an index.
 struct BatchShape {
   u32 max_actions = 0, max_roles = 0; bool ascending = true;
   u32 wide_lo = 0, wide_hi = 0;   // the requests with more than CBH_W2_NA actions or CBH_W2_NR roles lie in [wide_lo, wide_hi)
-  // Do the attribute columns hold plain scalars only - no int / uint (cross-type numerics) and no list / map (deep
-  // equality)?  Then no classified leaf can need the shared evaluator and the flat kernel without that call decides
-  // the batch (cbh_check_flat.h).  One pass over the tag bytes, made only where the answer selects a kernel and only
-  // when the first launch is being prepared - by then the uploads are enqueued and the pass runs beside them.
-  const uint8_t* tags = nullptr; size_t n_tags = 0;   // nullptr: the answer cannot matter (no flat kernel for this table / shape)
-  uint32_t sens_cols = 0; size_t n_req = 0;           // only these columns [bit c: tags + c * n_req] can send a classified leaf to the evaluator (CBH_M_SENS_COLS)
-  mutable std::atomic<int> plain{-1};                 // -1 not looked at yet (racing threads compute the same answer)
+  // plain tags (above): one pass over the tag bytes, made only where the answer selects a kernel and only when the first
+  // launch is being prepared - by then the uploads are enqueued and the pass runs beside them.
+  const uint8_t* tags = nullptr;             // [n_columns][n_req]; nullptr: the answer cannot matter (plain_tags_select)
+  const cbh_table* table = nullptr; uint32_t n_columns = 0; size_t n_req = 0;
+  mutable std::atomic<int> plain{-1};        // -1 not looked at yet (racing threads compute the same answer)
   bool plain_tags() const {
     int v = plain.load(std::memory_order_relaxed);
     if (v < 0) {
-      bool hit = false;
-      if (tags) for (uint32_t c = 0; c < 32 && !hit; ++c) if ((sens_cols >> c) & 1u) hit = has_int_or_container_tag(tags + (size_t)c * n_req, n_req);
+      const bool hit = tags && sens_tag_hit(table, tags, n_columns, n_req, [&](u32) { return TagRows{0, n_req}; });
       v = (!flat_any_forced() && !hit) ? 1 : 0;
       plain.store(v, std::memory_order_relaxed);
     }
     return v == 1;
   }
-  // tags 2, 3 (int, uint) and 6, 7 (list, map) are exactly the bytes x with (x & 0xFA) == 0x02: eight at a time
-  static bool has_int_or_container_tag(const uint8_t* p, size_t n) {
-    size_t i = 0; uint64_t hit = 0;
-    for (; i + 8 <= n; i += 8) {
-      uint64_t w; std::memcpy(&w, p + i, 8);
-      const uint64_t z = (w & 0xFAFAFAFAFAFAFAFAull) ^ 0x0202020202020202ull;              // a zero byte where a tag matched
-      hit |= (z - 0x0101010101010101ull) & ~z & 0x8080808080808080ull;
-    }
-    for (; i < n; ++i) hit |= (uint64_t)((p[i] & 0xFAu) == 0x02u);
-    return hit != 0;
-  }
+  PlanShape shape() const { return PlanShape{max_actions, max_roles, wide_lo, wide_hi, plain_tags()}; }   // (the late part: beside the uploads)
 };
 // the O(1) part of validate_batch: the arrays a batch of these counts needs are there
 static int validate_header(const cbh_table* t, const cbh_batch* in) {
@@ -80,12 +104,8 @@ static int validate_batch(const cbh_table* t, const cbh_batch* in, BatchShape& s
   if (in->n_strings && in->str_off[in->n_strings] > in->str_bytes_len) return fail("cbh_batch: string offsets exceed str_bytes_len");
   sh.max_actions = maxa; sh.max_roles = maxr; sh.ascending = !unordered;
   sh.wide_lo = whi ? wlo : 0; sh.wide_hi = whi;
-  sh.tags = nullptr; sh.n_tags = 0; sh.plain.store(-1, std::memory_order_relaxed);
-  // (a flat kernel decides the batch: four actions or, in the action groups cbh_plan takes, up to CBH_MAX_ACTIONS_PER_REQUEST)
-  if (((t->meta[CBH_M_FLAGS] & CBH_MF_FLAT) && maxr <= 4 && (maxa <= 4 || flat_groups_shape(t, maxa, maxr))) ||
-      ((t->meta[CBH_M_FLAGS] & CBH_MF_WALK2) && t->meta[CBH_M_GSLOTS_ALL] > t->meta[CBH_M_GSLOTS_GENERIC])) { sh.tags = in->col_tag; sh.n_tags = (size_t)in->n_columns * NR; }
-  sh.sens_cols = t->meta[CBH_M_SENS_COLS]; sh.n_req = NR;
-  if (in->n_columns < 32) sh.sens_cols &= (1u << in->n_columns) - 1u;
+  sh.table = t; sh.tags = plain_tags_select(t, maxa, maxr) ? in->col_tag : nullptr; sh.n_columns = in->n_columns; sh.n_req = NR;
+  sh.plain.store(-1, std::memory_order_relaxed);
   return 0;
 }
 
@@ -96,7 +116,7 @@ static bool compact_inputs_on() { static const bool on = env_int("CBH_COMPACT_IN
 static int batch_compact(cbh_device_batch* b, hipStream_t s) {
   const TableDev& dev = b->rep->dev;
   BatchDev& d = b->dev;
-  if (!compact_inputs_on() || !(dev.flags & CBH_MF_FLAT) || b->max_actions > 4 || b->max_roles > 4 || !d.n_requests) return 0;
+  if (!compact_inputs_on() || !(dev.flags & CBH_MF_FLAT) || b->shape.max_actions > 4 || b->shape.max_roles > 4 || !d.n_requests) return 0;
   CompactArgs ca{};
   ca.req_u32 = d.req_u32; ca.roles = d.roles; ca.tuple_action = d.tuple_action; ca.col_val = d.col_val; ca.col_tag = d.col_tag;
   ca.action_class = dev.action_class; ca.role_class = dev.role_class; ca.K = dev.K;
@@ -120,12 +140,12 @@ static int batch_compact(cbh_device_batch* b, hipStream_t s) {
 }
 
 // what a resident batch owns beside its inputs: glob bits, evaluation-site results, the result arrays, the launch arguments
-// (b->dev's counts and b->plain_tags are set).  gbits_words: three per batch-local string - or, for a wire batch of a table without
+// (b->dev's counts and b->shape are set).  gbits_words: three per batch-local string - or, for a wire batch of a table without
 // automata, whose dictionary has many slots and nobody to read their bits, one
 static int batch_device_buffers(cbh_device_batch* b, size_t gbits_words) {
   BatchDev& d = b->dev; const Replica* rep = b->rep;
   int rc = dalloc(b, d.gbits, gbits_words);
-  d.n_gwords = (rep->dev.flags & CBH_MF_WALK2) ? w2_gwords(rep->dev.gslots_generic, rep->dev.gslots_all, b->plain_tags) : 0;
+  d.n_gwords = (rep->dev.flags & CBH_MF_WALK2) ? w2_gwords(rep->dev.gslots_generic, rep->dev.gslots_all, b->shape.plain_tags) : 0;
   d.n_gslots = 0;   // per launch (launch_plan)
   if (d.n_gwords) rc |= dalloc(b, d.gres, (size_t)d.n_gwords * d.n_requests); else d.gres = nullptr;
   rc |= dalloc(b, b->out.effect, d.n_tuples);
@@ -159,6 +179,40 @@ static void batch_set_counts(cbh_device_batch* b, u32 n_requests, u32 n_tuples, 
   d.req_lo = 0; d.req_hi = n_requests;
 }
 
+// ---- what the makers of a resident batch share (batch_upload below; cross_upload, cross_pairs_upload: cbh_host_cross.h) ----
+// A batch that is still being made, made with cbh_batch_release as its deleter: released on every way out but the last, where batch_finish hands it out.
+typedef std::unique_ptr<cbh_device_batch, void (*)(cbh_device_batch*)> BatchOwner;
+// The six arrays a batch takes from its source as they are (`from`: a cbh_batch, or the BatchDev of a set's halves - `str_bytes_len`
+// is a count only the former keeps).  `copy(dst, src, n)`: up - from host memory - or dcopy, device to device.
+template <typename Source, typename Copy>
+static int batch_shared_arrays(BatchDev& d, const Source& from, size_t str_bytes_len, Copy copy) {
+  int rc = 0;
+  rc |= copy(d.roles, from.roles, from.n_roles);
+  rc |= copy(d.heap_tag, from.heap_tag, from.heap_len);
+  rc |= copy(d.heap_val, from.heap_val, from.heap_len);
+  rc |= copy(d.str_off, from.str_off, from.n_strings ? (size_t)from.n_strings + 1 : 0);
+  rc |= copy(d.str_bytes, from.str_bytes, str_bytes_len);
+  rc |= copy(d.str_flags, from.str_flags, from.n_strings);
+  d.tuple_req = nullptr;   // informational on the host side; no kernel reads it
+  return rc;
+}
+// The end of a maker.  `rc`: what its uploads and allocations returned so far (each has left its text); `launches`: what the maker
+// enqueues behind the cleared glob bits - its own kernels, then batch_compact where the batch may take the compact form.  The wait
+// is the last step: pageable host memory a maker copied from (the caller's arrays, a vector of the maker's frame) may go after it.
+template <typename Launches>
+static int batch_finish(BatchOwner& b, int rc, cbh_device_batch** out, Launches launches) {
+  BatchDev& d = b->dev; hipStream_t s = b->stream;
+  rc |= batch_device_buffers(b.get(), (size_t)3 * d.n_strings);
+  if (rc != 0) return -1;
+  // glob bits of the batch-local strings: all zero unless the table has automata to run (then
+  // cbh_check_resident overwrites every word on each launch)
+  if (d.n_strings && hipMemsetAsync(d.gbits, 0, (size_t)3 * d.n_strings * sizeof(u64), s) != hipSuccess) return fail("upload failed");
+  if (launches() != 0) return -1;
+  if (hipStreamSynchronize(s) != hipSuccess) return fail("upload failed");
+  *out = b.release();
+  return 0;
+}
+
 static int batch_upload(cbh_table* t, uint32_t device_index, const cbh_batch* in, cbh_device_batch** out, bool compact) {
   if (!t || !in || !out) return fail("null argument");
   if (device_index >= t->reps.size()) return fail("device index out of range");
@@ -166,161 +220,22 @@ static int batch_upload(cbh_table* t, uint32_t device_index, const cbh_batch* in
   if (validate_batch(t, in, sh) != 0) return -1;
   Replica* rep = t->reps[device_index];
   HIPCHK(hipSetDevice(rep->device));
-  cbh_device_batch* b = batch_new(t, rep, false);
+  BatchOwner b(batch_new(t, rep, false), cbh_batch_release);
   if (!b) return -1;
-  b->max_actions = sh.max_actions; b->max_roles = sh.max_roles; b->plain_tags = sh.plain_tags();
-  b->wide_lo = sh.wide_lo; b->wide_hi = sh.wide_hi;
+  b->shape = sh.shape();
   BatchDev& d = b->dev;
-  batch_set_counts(b, in->n_requests, in->n_tuples, in->n_roles, in->n_columns, in->n_strings, in->heap_len);
+  batch_set_counts(b.get(), in->n_requests, in->n_tuples, in->n_roles, in->n_columns, in->n_strings, in->heap_len);
   hipStream_t s = b->stream;
   const size_t NR = in->n_requests;
-  int rc = 0;
-  rc |= up(b, d.req_u32, in->req_u32, (size_t)CBH_RQ_NFIELDS * NR, s);
-  rc |= up(b, d.roles, in->roles, in->n_roles, s);
-  d.tuple_req = nullptr;   // informational on the host side; no kernel reads it
-  rc |= up(b, d.tuple_action, in->tuple_action, in->n_tuples, s);
-  rc |= up(b, d.col_tag, in->col_tag, (size_t)in->n_columns * NR, s);
-  rc |= up(b, d.col_val, in->col_val, (size_t)in->n_columns * NR, s);
-  rc |= up(b, d.heap_tag, in->heap_tag, in->heap_len, s);
-  rc |= up(b, d.heap_val, in->heap_val, in->heap_len, s);
-  rc |= up(b, d.str_off, in->str_off, in->n_strings ? (size_t)in->n_strings + 1 : 0, s);
-  rc |= up(b, d.str_bytes, in->str_bytes, in->str_bytes_len, s);
-  rc |= up(b, d.str_flags, in->str_flags, in->n_strings, s);
-  rc |= batch_device_buffers(b, (size_t)3 * d.n_strings);
-  if (rc != 0) { cbh_batch_release(b); return -1; }
-  // glob bits of the batch-local strings: all zero unless the table has automata to run (then
-  // cbh_check_resident overwrites every word on each launch)
-  if (in->n_strings && hipMemsetAsync(d.gbits, 0, (size_t)3 * in->n_strings * sizeof(u64), s) != hipSuccess) {
-    cbh_batch_release(b); return fail("upload failed");
-  }
-  if (compact && batch_compact(b, s) != 0) { cbh_batch_release(b); return -1; }
-  if (hipStreamSynchronize(s) != hipSuccess) { cbh_batch_release(b); return fail("upload failed"); }
-  *out = b;
-  return 0;
+  int rc = up(b.get(), d.req_u32, in->req_u32, (size_t)CBH_RQ_NFIELDS * NR, s);
+  rc |= up(b.get(), d.tuple_action, in->tuple_action, in->n_tuples, s);
+  rc |= up(b.get(), d.col_tag, in->col_tag, (size_t)in->n_columns * NR, s);
+  rc |= up(b.get(), d.col_val, in->col_val, (size_t)in->n_columns * NR, s);
+  rc |= batch_shared_arrays(d, *in, in->str_bytes_len, [&](auto& dst, auto* src, size_t n) { return up(b.get(), dst, src, n, s); });
+  return batch_finish(b, rc, out, [&] { return compact ? batch_compact(b.get(), s) : 0; });
 }
 extern "C" int cbh_batch_upload_on(cbh_table* t, uint32_t device_index, const cbh_batch* in, cbh_device_batch** out) { return batch_upload(t, device_index, in, out, true); }
 extern "C" int cbh_batch_upload(cbh_table* t, const cbh_batch* in, cbh_device_batch** out) { return cbh_batch_upload_on(t, 0, in, out); }
-
-// ---- cross-product batches: N + M halves up, the N x M product built in device memory (cbh_cross.h) ------------------------
-// The batch's shape comes from the halves, looking only at the rows the product uses, so that the product gets the plan a
-// host-built batch of the same requests gets (validate_batch's answers for that batch, without the batch).
-// (`bounded`: the product is materialised, so N * M and N * M * A must stay below 2^32 - the direct road, cbh_cross_upload, has no such bound)
-// (`plan_a`, set by the caller: the action count the plan is made for where it is not A - the direct road decides A > 4 four at a time)
-// (`group_roles`, set by the caller: the plan is made for at most four roles - the direct road decides more four at a time)
-struct CrossShape { std::vector<u8> side; u32 maxr = 0, wide_lo = 0, wide_hi = 0; bool plain = true; u32 plan_a = 0; bool group_roles = false; };
-static int cross_validate(cbh_table* t, uint32_t device_index, const cbh_batch* h, const cbh_cross* x, bool bounded, CrossShape& cs) {
-  if (device_index >= t->reps.size()) return fail("device index out of range");
-  const u64 N = x->n_principals, M = x->n_resources, A = x->n_actions;
-  if (!N || !M || !A) return fail("cbh_cross: n_principals, n_resources and n_actions must be at least 1");
-  if (A > CBH_MAX_ACTIONS_PER_REQUEST) return fail("cbh_cross: more than CBH_MAX_ACTIONS_PER_REQUEST actions");
-  if (!x->action_ids) return fail("null argument");
-  if ((u64)h->n_requests != N + M) return fail("cbh_cross: the halves batch must hold n_principals + n_resources requests");
-  if (bounded && (N * M >= (1ull << 32) || N * M * A >= (1ull << 32))) return fail("cbh_cross: the product has 2^32 requests or tuples, or more: split the resources");
-  const u32 ncol = h->n_columns;
-  if (ncol != t->meta[CBH_M_NCOLUMNS]) return fail("cbh_batch.n_columns does not match the table's column schema");
-  if (t->wire.cols.size() < ncol) return fail("the image names no column paths (CBH_SEC_COLUMN_PATHS): which half a column comes from is unknown");
-  if (!h->req_u32 || (h->n_roles && !h->roles) || (ncol && (!h->col_tag || !h->col_val)) || (h->heap_len && (!h->heap_tag || !h->heap_val)) ||
-      (h->n_strings && (!h->str_off || !h->str_flags)) || (h->str_bytes_len && !h->str_bytes)) return fail("cbh_batch: a required array is NULL");
-  if (h->n_strings && h->str_off[h->n_strings] > h->str_bytes_len) return fail("cbh_batch: string offsets exceed str_bytes_len");
-  const size_t NH = (size_t)(N + M), NM = (size_t)(N * M);
-  std::vector<u8>& side = cs.side; std::vector<u8> seen;
-  try { side.assign(ncol ? ncol : 1, 0); seen.assign(std::max(N, M), 0); } catch (...) { return fail("out of memory"); }
-  for (u32 c = 0; c < ncol; ++c) side[c] = t->wire.cols[c].root == 1 ? 1 : 0;
-  for (int which = 0; which < 2; ++which) {   // the orders are permutations
-    const uint32_t* ord = which ? x->r_order : x->p_order; const u64 cnt = which ? M : N;
-    if (!ord) continue;
-    std::fill(seen.begin(), seen.begin() + cnt, (u8)0);
-    for (u64 i = 0; i < cnt; ++i) {
-      if (ord[i] >= cnt || seen[ord[i]]) return fail(which ? "cbh_cross: r_order is not a permutation of 0 .. n_resources - 1" : "cbh_cross: p_order is not a permutation of 0 .. n_principals - 1");
-      seen[ord[i]] = 1;
-    }
-  }
-  // roles of the principals; where the requests wider than the walk's base shape lie in the product (validate_batch's wide_lo / wide_hi)
-  const u32* role_off = h->req_u32 + (size_t)CBH_RQ_ROLE_OFF * NH; const u32* role_cnt = h->req_u32 + (size_t)CBH_RQ_ROLE_CNT * NH;
-  u32 maxr = 0, bad = 0; u64 ilo = N, ihi = 0;   // device positions i' of the principals with more than CBH_W2_NR roles
-  for (u64 ip = 0; ip < N; ++ip) {
-    const size_t i = x->p_order ? x->p_order[ip] : ip;
-    maxr = role_cnt[i] > maxr ? role_cnt[i] : maxr;
-    bad |= (u32)((u64)role_off[i] + role_cnt[i] > (u64)h->n_roles);
-    if (role_cnt[i] > CBH_W2_NR) { if (ilo == N) ilo = ip; ihi = ip + 1; }
-  }
-  if (bad) return fail("cbh_batch: a request's role or action slice lies outside the batch");
-  u32 wide_lo = 0, wide_hi = 0;
-  if (A > CBH_W2_NA) wide_hi = (u32)NM;
-  else if (ihi) { wide_lo = (u32)ilo; wide_hi = (u32)((M - 1) * N + ihi); }
-  // plain tags: BatchShape::plain_tags over the rows the product uses
-  bool plain = true;
-  {
-    const u32 mf = t->meta[CBH_M_FLAGS];
-    const bool matters = ((mf & CBH_MF_FLAT) && ((cs.plan_a ? cs.plan_a : A) <= 4 || flat_groups_shape(t, (u32)A, maxr)) && (maxr <= 4 || cs.group_roles)) || ((mf & CBH_MF_WALK2) && t->meta[CBH_M_GSLOTS_ALL] > t->meta[CBH_M_GSLOTS_GENERIC]);
-    u32 sens = t->meta[CBH_M_SENS_COLS];
-    if (ncol < 32) sens &= (1u << ncol) - 1u;
-    bool hit = false;
-    if (matters) for (u32 c = 0; c < 32 && c < ncol && !hit; ++c) if ((sens >> c) & 1u)
-      hit = side[c] ? BatchShape::has_int_or_container_tag(h->col_tag + (size_t)c * NH + N, M) : BatchShape::has_int_or_container_tag(h->col_tag + (size_t)c * NH, N);
-    plain = !flat_any_forced() && !hit;
-  }
-  cs.maxr = maxr; cs.wide_lo = wide_lo; cs.wide_hi = wide_hi; cs.plain = plain;
-  return 0;
-}
-static int cross_upload(cbh_table* t, uint32_t device_index, const cbh_batch* h, const cbh_cross* x, cbh_device_batch** out) {
-  if (!t || !h || !x || !out) return fail("null argument");
-  *out = nullptr;
-  CrossShape cs;
-  if (cross_validate(t, device_index, h, x, true, cs) != 0) return -1;
-  const u64 N = x->n_principals, M = x->n_resources, A = x->n_actions;
-  const u32 ncol = h->n_columns;
-  const size_t NH = (size_t)(N + M), NM = (size_t)(N * M), NT = (size_t)(N * M * A);
-  const std::vector<u8>& side = cs.side;
-  const u32 maxr = cs.maxr, wide_lo = cs.wide_lo, wide_hi = cs.wide_hi; const bool plain = cs.plain;
-  Replica* rep = t->reps[device_index];
-  HIPCHK(hipSetDevice(rep->device));
-  cbh_device_batch* b = batch_new(t, rep, false);
-  if (!b) return -1;
-  b->max_actions = (u32)A; b->max_roles = maxr; b->plain_tags = plain; b->wide_lo = wide_lo; b->wide_hi = wide_hi;
-  BatchDev& d = b->dev;
-  batch_set_counts(b, (u32)NM, (u32)NT, h->n_roles, ncol, h->n_strings, h->heap_len);
-  hipStream_t s = b->stream;
-  CrossArgs ca{};
-  ca.n = (u32)N; ca.m = (u32)M; ca.a = (u32)A; ca.n_columns = ncol;
-  int rc = 0;
-  // the halves, the orders, the sides and the action ids (they stay with the batch until it is released: N + M rows)
-  rc |= up(b, ca.h_req, h->req_u32, (size_t)CBH_RQ_NFIELDS * NH, s);
-  rc |= up(b, ca.h_tag, h->col_tag, (size_t)ncol * NH, s);
-  rc |= up(b, ca.h_val, h->col_val, (size_t)ncol * NH, s);
-  if (x->p_order) rc |= up(b, ca.p_order, x->p_order, (size_t)N, s);
-  if (x->r_order) rc |= up(b, ca.r_order, x->r_order, (size_t)M, s);
-  rc |= up(b, ca.col_side, (const u8*)side.data(), (size_t)ncol, s);
-  rc |= up(b, ca.action_ids, x->action_ids, (size_t)A, s);
-  // shared as they are
-  rc |= up(b, d.roles, h->roles, h->n_roles, s);
-  rc |= up(b, d.heap_tag, h->heap_tag, h->heap_len, s);
-  rc |= up(b, d.heap_val, h->heap_val, h->heap_len, s);
-  rc |= up(b, d.str_off, h->str_off, h->n_strings ? (size_t)h->n_strings + 1 : 0, s);
-  rc |= up(b, d.str_bytes, h->str_bytes, h->str_bytes_len, s);
-  rc |= up(b, d.str_flags, h->str_flags, h->n_strings, s);
-  // the product
-  d.tuple_req = nullptr;
-  rc |= dalloc(b, ca.req, (size_t)CBH_RQ_NFIELDS * NM);
-  rc |= dalloc(b, ca.tag, (size_t)ncol * NM);
-  rc |= dalloc(b, ca.val, (size_t)ncol * NM);
-  rc |= dalloc(b, ca.tuple_action, NT);
-  rc |= batch_device_buffers(b, (size_t)3 * d.n_strings);
-  if (rc != 0) { cbh_batch_release(b); return -1; }
-  d.req_u32 = ca.req; d.col_tag = ca.tag; d.col_val = ca.val; d.tuple_action = ca.tuple_action;
-  if (h->n_strings && hipMemsetAsync(d.gbits, 0, (size_t)3 * h->n_strings * sizeof(u64), s) != hipSuccess) { cbh_batch_release(b); return fail("upload failed"); }
-  hipLaunchKernelGGL(cbh_cross_expand_kernel, dim3((u32)((NM + 255u) / 256u)), dim3(256), 0, s, ca);
-  hipLaunchKernelGGL(cbh_cross_actions_kernel, dim3((u32)(((NT + 3u) / 4u + 255u) / 256u)), dim3(256), 0, s, ca);
-  if (hipGetLastError() != hipSuccess) { cbh_batch_release(b); return fail("cross-product expansion failed to launch"); }
-  // (`side` is pageable memory of this frame: its copy must have left before the frame goes - batch_compact synchronises, or the wait below)
-  if (batch_compact(b, s) != 0) { cbh_batch_release(b); return -1; }
-  if (hipStreamSynchronize(s) != hipSuccess) { cbh_batch_release(b); return fail("upload failed"); }
-  *out = b;
-  return 0;
-}
-extern "C" int cbh_batch_upload_cross(cbh_table* t, uint32_t device_index, const cbh_batch* halves, const cbh_cross* x, cbh_device_batch** out) {
-  try { return cross_upload(t, device_index, halves, x, out); } catch (...) { return fail("out of memory"); }
-}
 
 static void collect_slot(Replica* r, Replica::Slot& sl) {   // the slot's last event has completed
   if (!sl.pending) return;
@@ -345,6 +260,7 @@ static CbhPlan plan_for(const TableDev& dev, u32 max_actions, u32 max_roles, boo
   return cbh_plan(dev.flags, dev.n_dr, has_globs, dev.gslots_generic, dev.gslots_all, max_actions, max_roles, plain_tags, eval_flags, no_flat, no_walk2,
                   force_staged ? 0xFFFFFFFFu : dev.max_bucket, no_walk2_wide, cbh_flat_use_masks(dev.segs, dev.max_bucket), action_groups && flat_action_groups_on());
 }
+static CbhPlan plan_for(const TableDev& dev, const PlanShape& sh, u32 eval_flags) { return plan_for(dev, sh.max_actions, sh.max_roles, sh.plain_tags, eval_flags); }   // (a batch's own plan)
 // (on by default since round 5: C5 11.8 -> 12.4 G decisions/s, C5W 7.61 -> 7.67, profiles/r05_presplit_ab.txt; CBH_PRE_SPLIT=0: the fused pre-pass)
 static bool pre_split_on() { static const bool on = env_int("CBH_PRE_SPLIT", 1) != 0; return on; }
 // Does the packed form of the column cache's tags (cbh_vm.h CBH_CC_DWORDS) let a CU hold more workgroups of `fn` than the wide one?
@@ -512,7 +428,7 @@ extern "C" int cbh_check_resident(cbh_table* t, cbh_device_batch* b, const cbh_p
   Replica::Slot& sl = timed ? rep->ring[rep->next_slot++ % Replica::RING] : scratch_slot;
   if (timed && sl.pending) { HIPCHK(hipEventSynchronize(sl.ev[3])); collect_slot(rep, sl); }
   const BatchDev& d = b->dev;
-  const CbhPlan pl = d.n_requests ? plan_for(rep->dev, b->max_actions, b->max_roles, b->plain_tags, p->flags) : CbhPlan{};
+  const CbhPlan pl = d.n_requests ? plan_for(rep->dev, b->shape, p->flags) : CbhPlan{};
   // A flat launch writes its results packed, a word per tuple, where the table's ids fit (not: the trail's kernels, the wire road's
   // batches - cbh_wire_outputs reads the wide arrays -, cycle-count launches); and for a table without derived roles no mask at all.
   // (action groups on a table with derived roles: a byte per request for the error of a definition, flat_body AGROUP)
@@ -545,7 +461,7 @@ extern "C" int cbh_check_resident(cbh_table* t, cbh_device_batch* b, const cbh_p
   }
   sl.pending = false;
   if (d.n_requests) {
-    launch_plan(pl, rep->dev, b->last_args, (const KernelArgs*)b->d_args, 0, d.n_requests, b->wide_lo, b->wide_hi, lds_pad(), s, timed ? sl.ev[2] : nullptr, timed ? sl.ev[3] : nullptr, b->dflag);
+    launch_plan(pl, rep->dev, b->last_args, (const KernelArgs*)b->d_args, 0, d.n_requests, b->shape.wide_lo, b->shape.wide_hi, lds_pad(), s, timed ? sl.ev[2] : nullptr, timed ? sl.ev[3] : nullptr, b->dflag);
     sl.pending = timed;
   }
   HIPCHK(hipGetLastError());
@@ -560,11 +476,11 @@ extern "C" int cbh_check_resident_many(cbh_table* t, cbh_device_batch* const* bs
   return 0;
 }
 
-// How many of the replica's resident streams batches uploaded FROM NOW ON are dealt to (1 .. 4; a batch keeps its stream).
+// How many of the replica's resident streams batches uploaded FROM NOW ON are dealt to (1 .. Replica::MAX_RESIDENT_STREAMS; a batch keeps its stream).
 // 1 = every launch queues behind the one before it: the setting for timing one kernel by itself.
 extern "C" int cbh_table_set_resident_streams(cbh_table* t, uint32_t n) {
   if (!t) return fail("null argument");
-  if (n < 1 || n > (uint32_t)Replica::MAX_RESIDENT_STREAMS) return fail("resident streams: 1 .. 8");
+  if (n < 1 || n > (uint32_t)Replica::MAX_RESIDENT_STREAMS) return fail("resident streams: 1 .. " + std::to_string(Replica::MAX_RESIDENT_STREAMS));
   for (Replica* rep : t->reps) { rep->n_rstreams.store((int)n); rep->next_rstream.store(0); }
   return 0;
 }
@@ -574,7 +490,7 @@ extern "C" uint32_t cbh_table_resident_streams(const cbh_table* t) { return t &&
 extern "C" const char* cbh_plan_describe(cbh_table* t, cbh_device_batch* b, const cbh_params* p) {
   static thread_local std::string s;
   if (!t || !b || !p) return "";
-  const CbhPlan pl = plan_for(b->rep->dev, b->max_actions, b->max_roles, b->plain_tags, p->flags & ~(u32)CBH_FI_MASK);
+  const CbhPlan pl = plan_for(b->rep->dev, b->shape, p->flags & ~(u32)CBH_FI_MASK);
   // (the pre-pass's form: cbh_check_resident's own condition for giving the batch its site lists)
   const Replica* rep = b->rep;
   const bool pre_split = pre_split_on() && b->dev.n_requests && (rep->dev.flags & CBH_MF_WALK2) && rep->dev.gslots_all && !(rep->dev.flags & CBH_MF_USES_RUNTIME_EDR) && b->dev.gres;
@@ -672,314 +588,6 @@ extern "C" int cbh_result_download_allow_bits(cbh_table* t, cbh_device_batch* b,
   HIPCHK(hipStreamSynchronize(s));
   collect_times(rep);
   return 0;
-}
-
-
-// ---- the direct cross road: N x M decided straight from the N + M halves (cerbos_hip.h cbh_cross_upload_ex / cbh_cross_check) ----
-// The set is the HALVES as a resident batch in its compact form (batch_upload + batch_compact, unchanged: the device holds N + M
-// rows, the wide arrays included - cbh_cross_pairs_upload gathers from them), the two orders, the columns' sides and the actions'
-// classes as one word per group of four.  A check launches the `_x` sibling of the kernel plan_for picks for (min(A, 4) actions,
-// the principals' roles, plain tags) with the compact launch's LDS, over the tile's N * (r_end - r_begin) pairs - once per group
-// of four actions, on the set's stream, each launch writing its own planes; what comes back is one ballot word per 64 pairs and
-// action.  The planes' device words belong to the set's batch (the replica's pool) and serve every tile that fits them.
-// A set whose principals have five to CBH_CX_MAX_ROLES roles (CBH_CX_ROLE_GROUPS) is uploaded with the principals' role counts
-// clamped to four - the compact record then holds a principal's first four roles, group 0 - and keeps one role word per principal
-// and further group of four roles (cbh_cross_role_word_kernel); a check launches, per group of actions, role group 0, then 1, 2, ...
-// of the same kernel, each ORing into the planes what the groups before it left open (flat_body CROSS).
-struct cbh_cross_set {
-  cbh_device_batch* b = nullptr;
-  u32 n = 0, m = 0, a = 0, maxr = 0; bool plain = true;
-  const u32* p_order = nullptr; const u32* r_order = nullptr;   // device, or null = identity
-  u32 side = 0;                                                   // the cached columns' sides as a mask (CrossDev.side)
-  std::vector<u32> act_words;                                     // one per group of four actions (cbh_cross_act_word_kernel)
-  u64* planes = nullptr; size_t plane_cap = 0;   // [allow | flagged][a][words]
-  // what cbh_cross_pairs_upload needs beside the halves' own arrays: every column's side and the action ids on the device, the
-  // principals' role counts by device position (the shape of a batch of chosen pairs), the length of the strings' bytes
-  const u8* d_side = nullptr; const u32* d_act = nullptr;
-  std::vector<u8> p_roles; u32 str_bytes_len = 0;
-  // a set with role groups (maxr > 4): [(groups - 1)][n] role words and [n] class masks of all roles, by halves row (CrossRoleGroup), and the
-  // principals' true role counts by halves row for the gather (the halves' request words on the device hold them clamped)
-  const u32* role_words = nullptr; const u32* rc_all = nullptr; const u32* d_role_cnt = nullptr;
-  const CrossRoleGroup* d_rg = nullptr;   // ... and the launches' records, one per role group (CrossDev.rg)
-};
-static u32 cross_groups(const cbh_cross_set* cs) { return (cs->a + 3u) / 4u; }
-static u32 cross_role_groups(const cbh_cross_set* cs) { return cs->maxr > 4u ? (cs->maxr + 3u) / 4u : 1u; }
-// The flagged planes are the status of the materialised product, and the kernels that decide a product of wide requests do not agree
-// on where an error of a derived-role definition is marked (cbh_check_flat.h flat_body): from how many roles on a principal's
-// requests would be decided by the general walk, by the product's own plan (launch_plan: CBH_FI_ONLY_WIDE / CBH_FI_ONLY_WIDER).
-// (The flags that change a product's plan - strict evaluation, the trail - have no direct form: the plan under flags 0 is the one.)
-static u32 cross_open_from(const TableDev& dev, const cbh_cross_set* cs) {
-  const CbhPlan pp = plan_for(dev, cs->a, cs->maxr, cs->plain, 0, false);   // (the marks' places are those of the plan without action groups, which the groups reproduce)
-  if (pp.kind == 0) return 0u;
-  if (pp.kind != 2 || !pp.wide_kernel) return 0xFFFFFFFFu;
-  if (pp.walk_wide || pp.walk_awide) return cs->a > CBH_W2_AWIDE_NA ? 0u : cs->a > CBH_W2_NA ? CBH_W2_NR + 1u : CBH_W2_WIDE_NR + 1u;   // cbh_is_wider
-  return cs->a > CBH_W2_NA ? 0u : CBH_W2_NR + 1u;                                                                                          // cbh_is_wide
-}
-static cbh_cross_kernel_fn cross_kernel_for(const cbh_cross_set* cs, u32 eval_flags, CbhPlan& pl) {
-  // (for at most four roles: with more, plan_for picks a walk kernel, which has no `_x` variant)
-  pl = plan_for(cs->b->rep->dev, std::min(cs->a, 4u), std::min(cs->maxr, 4u), cs->plain, eval_flags & ~(u32)CBH_FI_MASK);
-  if (pl.kind != 1 || (eval_flags & CBH_F_DEBUG_CYCLES)) return nullptr;
-  return cbh_flat_cross_variant(pl.kernel);
-}
-static int cross_set_upload(cbh_table* t, uint32_t device_index, const cbh_batch* h, const cbh_cross* x, uint32_t accept, cbh_cross_set** out) {
-  if (out) *out = nullptr;
-  if (!t || !h || !x || !out) return fail("null argument");
-  if (accept & ~(uint32_t)(CBH_CX_DERIVED_ROLES | CBH_CX_ACTION_GROUPS | CBH_CX_ROLE_GROUPS)) return fail("cbh_cross_upload_ex: `accept` has a bit this library does not know");
-  CrossShape shape;
-  shape.plan_a = std::min(x->n_actions, 4u);
-  shape.group_roles = (accept & CBH_CX_ROLE_GROUPS) != 0;
-  if (cross_validate(t, device_index, h, x, false, shape) != 0) return -1;
-  Replica* rep = t->reps[device_index];
-  const u32 N = x->n_principals, M = x->n_resources, A = x->n_actions;
-  // no direct form: the caller takes cbh_batch_upload_cross, which gives the same answers
-  if (!(rep->dev.flags & CBH_MF_FLAT)) { g_err = "cbh_cross_upload: no direct form - the table is not flat"; return 1; }
-  if (rep->dev.n_dr && !(accept & CBH_CX_DERIVED_ROLES)) { g_err = "cbh_cross_upload: no direct form - the table has derived roles"; return 1; }
-  if (A > 4 && !(accept & CBH_CX_ACTION_GROUPS)) { g_err = "cbh_cross_upload: no direct form - more than four actions"; return 1; }
-  if (shape.maxr > 4 && !(accept & CBH_CX_ROLE_GROUPS)) { g_err = "cbh_cross_upload: no direct form - a principal has more than four roles"; return 1; }
-  if (shape.maxr > CBH_CX_MAX_ROLES) { g_err = "cbh_cross_upload: no direct form - a principal has more than CBH_CX_MAX_ROLES (16) roles"; return 1; }
-  if (!shape.plain) { g_err = "cbh_cross_upload: no direct form - an attribute value needs the evaluator (int / uint / list / map in a sensitive column)"; return 1; }
-  if (!compact_inputs_on()) { g_err = "cbh_cross_upload: no direct form - compact inputs are switched off"; return 1; }
-  {   // the kernel the product would be planned (mask walk of a table that is not closed over the classified leaves: cbh_flat_cross_mode)
-    const CbhPlan pl = plan_for(rep->dev, shape.plan_a, std::min(shape.maxr, 4u), shape.plain, 0);
-    if (pl.kind != 1 || !cbh_flat_cross_variant(pl.kernel)) { g_err = "cbh_cross_upload: no direct form - the kernel planned for this table has no direct instantiation"; return 1; }
-  }
-  cbh_cross_set* cs = new (std::nothrow) cbh_cross_set();
-  if (!cs) return fail("out of memory");
-  cs->n = N; cs->m = M; cs->a = A; cs->maxr = shape.maxr; cs->plain = shape.plain; cs->str_bytes_len = h->str_bytes_len;
-  for (u32 c = 0; c < h->n_columns && c < CBH_CACHE_COLS; ++c) if (shape.side[c]) cs->side |= 1u << c;
-  const size_t NH = (size_t)N + M;
-  cs->p_roles.resize(N);
-  for (u32 ip = 0; ip < N; ++ip) cs->p_roles[ip] = (u8)h->req_u32[(size_t)CBH_RQ_ROLE_CNT * NH + (x->p_order ? x->p_order[ip] : ip)];   // (<= CBH_CX_MAX_ROLES: checked above)
-  // The halves' OWN actions are not read by any road of a set, but a row that carries more than four of them has no compact
-  // record (cbh_compact_scan_kernel) - and the flattener hands the set's A actions to the first row.  A set of action groups
-  // therefore uploads the request words with such rows' action counts cleared; a set of up to four actions is uploaded as it is.
-  // Likewise a principal's row with more than four roles: a set of role groups uploads it with the count clamped to four, so that
-  // its record holds the first four roles (the slices were checked by cross_validate; the resources' rows stay as they are).
-  cbh_batch hh = *h;
-  std::vector<u32> req_copy;
-  if (A > 4 || shape.maxr > 4) req_copy.assign(h->req_u32, h->req_u32 + (size_t)CBH_RQ_NFIELDS * NH);
-  if (shape.maxr > 4) {
-    u32* cnt = req_copy.data() + (size_t)CBH_RQ_ROLE_CNT * NH;
-    for (size_t r = 0; r < N; ++r) cnt[r] = std::min(cnt[r], 4u);
-    hh.req_u32 = req_copy.data();
-  }
-  if (A > 4) {
-    u32* cnt = req_copy.data() + (size_t)CBH_RQ_ACT_CNT * NH;
-    for (size_t r = 0; r < NH; ++r) if (cnt[r] > 4u && (u64)req_copy[(size_t)CBH_RQ_ACT_OFF * NH + r] + cnt[r] <= (u64)h->n_tuples) cnt[r] = 0;   // (a slice outside the batch stays, to be refused)
-    hh.req_u32 = req_copy.data();
-  }
-  // the halves: an ordinary resident batch of N + M requests (validated as one: the scan and the pack read every row's role and
-  // action slices) with its compact form
-  if (batch_upload(t, device_index, &hh, &cs->b, true) != 0) { delete cs; return -1; }
-  cbh_device_batch* b = cs->b;
-  auto drop = [&](int rc) { cbh_batch_release(b); delete cs; return rc; };
-  b->max_actions = A; b->max_roles = shape.maxr; b->plain_tags = shape.plain;   // (the PRODUCT's shape; the plan is made for min(A, 4) actions: cross_kernel_for)
-  if (!b->compact) { g_err = "cbh_cross_upload: no direct form - a field of the halves does not fit the compact record (CBH_CI_MISFIT)"; return drop(1); }
-  hipStream_t s = b->stream;
-  u32* d_word = nullptr;
-  const u32 G = cross_groups(cs);
-  cs->act_words.assign(G, 0u);
-  int rc = 0;
-  if (x->p_order) rc |= up(b, cs->p_order, x->p_order, (size_t)N, s);
-  if (x->r_order) rc |= up(b, cs->r_order, x->r_order, (size_t)M, s);
-  rc |= up(b, cs->d_act, x->action_ids, (size_t)A, s);
-  rc |= up(b, cs->d_side, (const u8*)shape.side.data(), (size_t)h->n_columns, s);   // (pageable memory of this frame: the wait below)
-  rc |= dalloc(b, d_word, G);
-  const u32 R = cross_role_groups(cs);
-  u32* d_rw = nullptr; u32* d_all = nullptr;
-  if (R > 1) {
-    rc |= up(b, cs->d_role_cnt, h->req_u32 + (size_t)CBH_RQ_ROLE_CNT * NH, (size_t)N, s);   // (the caller's words: the true counts)
-    rc |= dalloc(b, d_rw, (size_t)(R - 1) * N);
-    rc |= dalloc(b, d_all, (size_t)N);
-  }
-  if (rc != 0) return drop(-1);
-  if (R > 1) {
-    CrossRoleWordArgs ra{}; ra.role_off = b->dev.req_u32 + (size_t)CBH_RQ_ROLE_OFF * NH; ra.role_cnt = cs->d_role_cnt; ra.roles = b->dev.roles;
-    ra.role_class = rep->dev.role_class; ra.words = d_rw; ra.all = d_all; ra.n = N; ra.groups = R; ra.K = rep->dev.K;
-    hipLaunchKernelGGL(cbh_cross_role_word_kernel, dim3((N + 255u) / 256u), dim3(256), 0, s, ra);
-    cs->role_words = d_rw; cs->rc_all = d_all;
-    std::vector<CrossRoleGroup> recs(R);   // (pageable memory of this frame: the wait below)
-    const u32 open_from = cross_open_from(rep->dev, cs);
-    for (u32 g = 0; g < R; ++g) recs[g] = CrossRoleGroup{g ? d_rw + (size_t)(g - 1u) * N : nullptr, d_all, cs->d_role_cnt, g, open_from};
-    if (up(b, cs->d_rg, recs.data(), (size_t)R, s) != 0 || hipStreamSynchronize(s) != hipSuccess) { (void)hipGetLastError(); fail("cbh_cross_upload: upload failed"); return drop(-1); }
-  }
-  CrossActWordArgs wa{}; wa.action_ids = cs->d_act; wa.action_class = rep->dev.action_class; wa.out = d_word; wa.a = A; wa.K = rep->dev.K;
-  hipLaunchKernelGGL(cbh_cross_act_word_kernel, dim3(1), dim3(64), 0, s, wa);
-  if (hipGetLastError() != hipSuccess || hipMemcpyAsync(cs->act_words.data(), d_word, (size_t)G * 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
-    (void)hipGetLastError(); fail("cbh_cross_upload: upload failed"); return drop(-1);
-  }
-  *out = cs;
-  return 0;
-}
-extern "C" int cbh_cross_upload_ex(cbh_table* t, uint32_t device_index, const cbh_batch* halves, const cbh_cross* x, uint32_t accept, cbh_cross_set** out) {
-  try { return cross_set_upload(t, device_index, halves, x, accept, out); } catch (...) { return fail("out of memory"); }
-}
-extern "C" int cbh_cross_upload(cbh_table* t, uint32_t device_index, const cbh_batch* halves, const cbh_cross* x, cbh_cross_set** out) {
-  return cbh_cross_upload_ex(t, device_index, halves, x, 0, out);
-}
-static int cross_set_check(cbh_table* t, cbh_cross_set* cs, const cbh_params* p, uint32_t r_begin, uint32_t r_end, uint64_t* allow, uint64_t* flagged, size_t words_per_plane) {
-  if (!t || !cs || !p || !allow) return fail("null argument");
-  cbh_device_batch* b = cs->b;
-  if (b->table != t) return fail("the set was uploaded for a different table");
-  if (r_begin >= r_end || r_end > cs->m) return fail("cbh_cross_check: [r_begin, r_end) must be a non-empty range of the set's resources");
-  const u64 nt = (u64)cs->n * (r_end - r_begin);
-  if (nt >= (1ull << 32)) return fail("cbh_cross_check: the tile has 2^32 requests or more: take fewer resources");
-  const size_t W = (size_t)((nt + 63) / 64);
-  if (words_per_plane < W) return fail("cbh_cross_check: words_per_plane is less than (n_principals * (r_end - r_begin) + 63) / 64");
-  CbhPlan pl;
-  const cbh_cross_kernel_fn fn = cross_kernel_for(cs, p->flags, pl);
-  if (!fn) { g_err = "cbh_cross_check: these flags choose a plan without a direct form"; return 1; }
-  Replica* rep = b->rep;
-  std::lock_guard<std::mutex> lk(rep->mu);
-  HIPCHK(hipSetDevice(rep->device));
-  hipStream_t s = b->stream;
-  const size_t per = (size_t)cs->a * W, need = per * (flagged ? 2 : 1);
-  if (need > cs->plane_cap) {
-    // a larger tile than any before: a new block, and the old one back to the replica's pool (every check ends with a wait for its
-    // copies, so nothing of the stream still reads it)
-    u64* np = nullptr;
-    if (dalloc(b, np, need) != 0) return -1;
-    if (cs->planes) {
-      for (size_t i = 0; i < b->allocs.size(); ++i) if (b->allocs[i].first == (void*)cs->planes) {
-        { std::lock_guard<std::mutex> pl(rep->pool_mu); rep->pool_free.push_back(b->allocs[i]); }
-        b->allocs[i] = b->allocs.back(); b->allocs.pop_back();
-        break;
-      }
-    }
-    cs->planes = np; cs->plane_cap = need;
-  }
-  KernelArgs ka;
-  std::memset(&ka, 0, sizeof(ka));
-  ka.t = rep->dev; ka.b = b->dev; ka.now_ns = p->now_ns;
-  ka.flags = (p->flags & ~(u32)CBH_FI_MASK) | CBH_FI_COMPACT | CBH_FI_PACKED_TAGS;   // (a compact launch: the cache's tags in the packed form)
-  CrossDev x{};
-  x.p_order = cs->p_order; x.r_order = cs->r_order;
-  x.n = cs->n; x.r_begin = r_begin; x.n_tile = (u32)nt; x.words = (u32)W; x.side = cs->side;
-  const TableDev& dev = rep->dev;
-  const size_t lds = cbh_plan_lds(pl, dev.flags, dev.max_depth, dev.n_scopes, dev.K, ka.b.n_columns, dev.inline_cols, dev.n_dr, false, CBH_W2_NA, true) + lds_pad();
-  // one launch per group of four actions, each with the group's word and its own planes [4 g, 4 g + 4) of the block - and within it
-  // one per group of four roles, in order: group 0 stores its ballots, every later one ORs into them what the earlier ones left open
-  const u32 R = cross_role_groups(cs);
-  for (u32 g = 0; g < cross_groups(cs); ++g) {
-    x.act_word = cs->act_words[g];
-    x.allow = cs->planes + (size_t)4 * g * W; x.flagged = flagged ? cs->planes + per + (size_t)4 * g * W : nullptr;
-    for (u32 rg = 0; rg < R; ++rg) {
-      x.rg = cs->d_rg ? cs->d_rg + rg : nullptr;   // (null in a set without role groups: exactly the launch such a set always had)
-      hipLaunchKernelGGL(fn, dim3((u32)((nt + pl.threads - 1) / pl.threads)), dim3(pl.threads), lds, s, ka, (const KernelArgs*)nullptr, x);   // (the arguments in memory are the evaluator call's: no _x kernel has one)
-    }
-  }
-  HIPCHK(hipGetLastError());
-  for (int which = 0; which < (flagged ? 2 : 1); ++which) {
-    uint64_t* dst = which ? flagged : allow; const u64* src = cs->planes + (size_t)which * per;
-    if (words_per_plane == W) HIPCHK(hipMemcpyAsync(dst, src, per * 8, hipMemcpyDeviceToHost, s));
-    else for (u32 k = 0; k < cs->a; ++k) HIPCHK(hipMemcpyAsync(dst + (size_t)k * words_per_plane, src + (size_t)k * W, W * 8, hipMemcpyDeviceToHost, s));
-  }
-  HIPCHK(hipStreamSynchronize(s));
-  return 0;
-}
-extern "C" int cbh_cross_check(cbh_table* t, cbh_cross_set* cs, const cbh_params* p, uint32_t r_begin, uint32_t r_end, uint64_t* allow, uint64_t* flagged, size_t words_per_plane) {
-  try { return cross_set_check(t, cs, p, r_begin, r_end, allow, flagged, words_per_plane); } catch (...) { return fail("out of memory"); }
-}
-extern "C" const char* cbh_cross_describe(cbh_table* t, cbh_cross_set* cs, const cbh_params* p) {
-  static thread_local std::string s;
-  if (!t || !cs || !p) return "";
-  try {
-    CbhPlan pl;
-    if (cs->b->table != t) s = "none: the set was uploaded for a different table";
-    else if (!cross_kernel_for(cs, p->flags, pl)) s = "none: these flags choose a plan without a direct form";
-    else {
-      char m[160], g[40] = "", r[40] = "";
-      if (cross_groups(cs) > 1) snprintf(g, sizeof g, ", %u action groups", cross_groups(cs));
-      if (cross_role_groups(cs) > 1) snprintf(r, sizeof r, ", %u role groups", cross_role_groups(cs));
-      snprintf(m, sizeof m, "[direct cross, %u + %u rows, narrow columns 0x%x%s%s]", cs->n, cs->m, cs->b->dev.compact_info & CBH_CI_NARROW_MASK, g, r);
-      s = std::string(cbh_flat_cross_name(pl.kernel)) + m;
-    }
-  } catch (...) { return ""; }
-  return s.c_str();
-}
-extern "C" void cbh_cross_release(cbh_cross_set* cs) {
-  if (!cs) return;
-  cbh_batch_release(cs->b);
-  delete cs;
-}
-
-// Chosen pairs of a set - the flagged ones, as a rule - as an ordinary resident batch built on the device from the set's own rows
-// (cbh_cross_gather_kernel), by cross_upload's steps: the same constructor, counts, buffers and compact form, and the shape a
-// host-built batch of those requests would get.  Roles, heap and strings are copied device to device: the batch outlives the set.
-template <typename T>
-static int dcopy(cbh_device_batch* b, const T*& dst, const T* src, size_t n, hipStream_t s) {
-  T* p = nullptr; dst = nullptr;
-  if (dalloc(b, p, n) != 0) return -1;
-  if (n) HIPCHK(hipMemcpyAsync(p, src, n * sizeof(T), hipMemcpyDeviceToDevice, s));
-  dst = p;
-  return 0;
-}
-static int cross_pairs_upload(cbh_table* t, cbh_cross_set* cs, const uint32_t* pair_p, const uint32_t* pair_r, uint32_t n_pairs, cbh_device_batch** out) {
-  if (out) *out = nullptr;
-  if (!t || !cs || !pair_p || !pair_r || !out) return fail("null argument");
-  cbh_device_batch* hb = cs->b;
-  if (hb->table != t) return fail("the set was uploaded for a different table");
-  if (!n_pairs) return fail("cbh_cross_pairs_upload: n_pairs must be at least 1");
-  const u64 NP = n_pairs, A = cs->a;
-  if (NP * A >= (1ull << 32)) return fail("cbh_cross_pairs_upload: the batch has 2^32 tuples or more: take fewer pairs");
-  u32 maxr = 0;
-  for (u32 q = 0; q < n_pairs; ++q) {   // before anything is launched: the kernel indexes the set's rows with these
-    if (pair_p[q] >= cs->n || pair_r[q] >= cs->m) return fail("cbh_cross_pairs_upload: a pair's index is outside the set (pair_p < n_principals, pair_r < n_resources, device order)");
-    maxr = std::max(maxr, (u32)cs->p_roles[pair_p[q]]);
-  }
-  Replica* rep = hb->rep;
-  HIPCHK(hipSetDevice(rep->device));
-  cbh_device_batch* b = batch_new(t, rep, false);
-  if (!b) return -1;
-  const BatchDev& hd = hb->dev;
-  const u32 ncol = hd.n_columns;
-  b->max_actions = (u32)A; b->max_roles = maxr; b->plain_tags = cs->plain;   // (every row of a set holds plain values)
-  // where the requests wider than the walk's base shape lie (validate_batch's wide_lo / wide_hi): every pair of a set of more than
-  // CBH_W2_NA actions, else the pairs whose principal has more than CBH_W2_NR roles (a set with role groups)
-  b->wide_lo = 0; b->wide_hi = A > CBH_W2_NA ? n_pairs : 0;
-  if (A <= CBH_W2_NA && maxr > CBH_W2_NR) {
-    u32 wlo = n_pairs, whi = 0;
-    for (u32 q = 0; q < n_pairs; ++q) if (cs->p_roles[pair_p[q]] > CBH_W2_NR) { if (wlo == n_pairs) wlo = q; whi = q + 1; }
-    b->wide_lo = wlo; b->wide_hi = whi;
-  }
-  BatchDev& d = b->dev;
-  batch_set_counts(b, n_pairs, (u32)(NP * A), hd.n_roles, ncol, hd.n_strings, hd.heap_len);
-  hipStream_t s = b->stream;
-  CrossGatherArgs ga{};
-  ga.h_req = hd.req_u32; ga.h_tag = hd.col_tag; ga.h_val = hd.col_val; ga.p_order = cs->p_order; ga.r_order = cs->r_order; ga.col_side = cs->d_side;
-  ga.p_role_cnt = cs->d_role_cnt;   // (a set with role groups: the true counts; else null - the request words')
-  ga.n = cs->n; ga.nh = cs->n + cs->m; ga.n_pairs = n_pairs; ga.a = (u32)A; ga.n_columns = ncol;
-  CrossArgs ca{};   // (for cbh_cross_actions_kernel: a product of n_pairs x 1)
-  ca.n = n_pairs; ca.m = 1; ca.a = (u32)A; ca.action_ids = cs->d_act;
-  int rc = 0;
-  rc |= up(b, ga.pair_p, pair_p, (size_t)n_pairs, s);
-  rc |= up(b, ga.pair_r, pair_r, (size_t)n_pairs, s);
-  rc |= dcopy(b, d.roles, hd.roles, hd.n_roles, s);
-  rc |= dcopy(b, d.heap_tag, hd.heap_tag, hd.heap_len, s);
-  rc |= dcopy(b, d.heap_val, hd.heap_val, hd.heap_len, s);
-  rc |= dcopy(b, d.str_off, hd.str_off, hd.n_strings ? (size_t)hd.n_strings + 1 : 0, s);
-  rc |= dcopy(b, d.str_bytes, hd.str_bytes, cs->str_bytes_len, s);
-  rc |= dcopy(b, d.str_flags, hd.str_flags, hd.n_strings, s);
-  d.tuple_req = nullptr;
-  rc |= dalloc(b, ga.req, (size_t)CBH_RQ_NFIELDS * NP);
-  rc |= dalloc(b, ga.tag, (size_t)ncol * NP);
-  rc |= dalloc(b, ga.val, (size_t)ncol * NP);
-  rc |= dalloc(b, ca.tuple_action, (size_t)(NP * A));
-  rc |= batch_device_buffers(b, (size_t)3 * d.n_strings);
-  if (rc != 0) { cbh_batch_release(b); return -1; }
-  d.req_u32 = ga.req; d.col_tag = ga.tag; d.col_val = ga.val; d.tuple_action = ca.tuple_action;
-  if (d.n_strings && hipMemsetAsync(d.gbits, 0, (size_t)3 * d.n_strings * sizeof(u64), s) != hipSuccess) { cbh_batch_release(b); return fail("upload failed"); }
-  hipLaunchKernelGGL(cbh_cross_gather_kernel, dim3((n_pairs + 255u) / 256u), dim3(256), 0, s, ga);
-  hipLaunchKernelGGL(cbh_cross_actions_kernel, dim3((u32)(((NP * A + 3u) / 4u + 255u) / 256u)), dim3(256), 0, s, ca);
-  if (hipGetLastError() != hipSuccess) { cbh_batch_release(b); return fail("cbh_cross_pairs_upload: the gather failed to launch"); }
-  // (the pair lists are the caller's pageable memory: their copies must have left before the call returns - batch_compact synchronises, or the wait below)
-  if (batch_compact(b, s) != 0) { cbh_batch_release(b); return -1; }
-  if (hipStreamSynchronize(s) != hipSuccess) { cbh_batch_release(b); return fail("upload failed"); }
-  *out = b;
-  return 0;
-}
-extern "C" int cbh_cross_pairs_upload(cbh_table* t, cbh_cross_set* set, const uint32_t* pair_p, const uint32_t* pair_r, uint32_t n_pairs, cbh_device_batch** out) {
-  try { return cross_pairs_upload(t, set, pair_p, pair_r, n_pairs, out); } catch (...) { return fail("out of memory"); }
 }
 
 

@@ -1,4 +1,4 @@
-// Host side of libcerbos_hip.so, part 3 of 4 (included by cbh_engine.hip, host pass only): the wire road.
+// Host side of libcerbos_hip.so, part 4 of 5 (included by cbh_engine.hip, host pass only): the wire road.
 #pragma once
 
 // ---- device-side ingest: serialized CheckInputs -> a resident batch, flattened by the GPU (cbh_wire.h) ------------------
@@ -401,8 +401,8 @@ static int wf_finish(WireFlatten& f, cbh_device_batch** out) {
   b->w.req_input = a.req_u32;
   d.heap_tag = a.heap_tag; d.heap_val = a.heap_val; d.str_off = nullptr; d.str_bytes = f.d_msg; d.str_flags = (const u8*)a.lflags; d.str_keys = a.lix;
   b->w.in_span = a.in_span; b->w.act_span = a.act_span; b->w.moff = f.d_moff; b->w.dver_off = a.dver_off; b->w.dver_len = a.dver_len;
-  b->max_actions = st.max_actions; b->max_roles = st.max_roles; b->plain_tags = !flat_any_forced() && !(st.flags & CBH_WF_CONTAINER_IN_SENS);
-  b->wide_lo = st.wide_hi ? st.wide_lo : 0; b->wide_hi = st.wide_hi;
+  const bool plain = !flat_any_forced() && !(st.flags & CBH_WF_CONTAINER_IN_SENS);
+  b->shape = PlanShape{st.max_actions, st.max_roles, st.wide_hi ? st.wide_lo : 0, st.wide_hi, plain};
   const bool globs = nfa_maxw(rep->dev) != 0;   // (no automata: nobody reads the glob bits, one word stands for them)
   if (batch_device_buffers(b, globs ? (size_t)3 * f.slots : (size_t)1) != 0) return -1;
   if (globs && hipMemsetAsync(d.gbits, 0, (size_t)3 * f.slots * sizeof(u64), f.s) != hipSuccess) return fail("cbh_wire_flatten: memset failed");
@@ -411,7 +411,7 @@ static int wf_finish(WireFlatten& f, cbh_device_batch** out) {
   if (f.try_group && pin_routes[1] == 0u && pin_routes[0] > 1u) {   // grouped (not: a full route table, or one route - nothing to group)
     d.req_u32 = f.ra.req_out; d.col_tag = f.ra.col_tag_out; d.col_val = f.ra.col_val_out;
     b->w.inv = f.ra.inv;
-    if (b->wide_hi) { b->wide_lo = 0; b->wide_hi = n; }   // the wider requests lie anywhere now: their launch skips the others lane by lane
+    if (b->shape.wide_hi) { b->shape.wide_lo = 0; b->shape.wide_hi = n; }   // the wider requests lie anywhere now: their launch skips the others lane by lane
     info->n_routes = pin_routes[0];
   }
   *out = b; f.b = nullptr;

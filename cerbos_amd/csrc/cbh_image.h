@@ -91,6 +91,10 @@ static inline const char* cbh_parse_image(TableDev& d, std::vector<uint32_t>& me
     const CbhBlobSection* ps = find(CBH_SEC_SCOPE_PARENT);
     const uint32_t ns = m[CBH_M_NSCOPES];
     if (!ps || ps->nbytes < (uint64_t)ns * 4) return ("blob scope section too small");
+    // (the kernels read scope_flags[0] for a request whose scope the table does not know: cbh_kernels.h chain_first)
+    const CbhBlobSection* fs = find(CBH_SEC_SCOPE_FLAGS);
+    if (ns == 0) return ("blob has no scope");
+    if (!fs || fs->nbytes < (uint64_t)ns * 4) return ("blob scope flags section too small");
     const uint32_t* par = reinterpret_cast<const uint32_t*>(host_copy + ps->offset);
     uint32_t deepest = 1;
     for (uint32_t s = 0; s < ns; ++s) {

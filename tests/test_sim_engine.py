@@ -181,6 +181,33 @@ def test_smoke_body(engine):
     g.smoke()
 
 
+def test_images_without_scope_flags_are_refused(engine):
+    """The kernels read scope_flags[0] for a request whose scope the table does not know (cbh_kernels.h chain_first), so an image
+    must have a scope and a flag word for each: C1's image with its scope count set to 0, and with its CBH_SEC_SCOPE_FLAGS section
+    one byte short of n_scopes words, are refused at load with a text (nothing is decided with them); the image itself loads."""
+    import struct
+
+    from cerbos_amd import workloads
+    from cerbos_amd.lower import blob as lb
+    from test_cross_device import _lower
+    good = bytes(_lower(workloads.c1_policies()).blob)
+    _, _, n_sections = struct.unpack_from("<III", good, 0)
+    sections = {}
+    for i in range(n_sections):
+        sid, _, off, nbytes, _ = struct.unpack_from("<IIQQQ", good, 32 + 32 * i)
+        sections[sid] = (32 + 32 * i, off, nbytes)
+    n_scopes = struct.unpack_from("<I", good, sections[lb.SEC_META][1] + 4 * lb.M_NSCOPES)[0]
+    assert n_scopes >= 1 and sections[lb.SEC_SCOPE_FLAGS][2] >= 4 * n_scopes
+    engine.Table(good).close()
+    no_scope, short_flags = bytearray(good), bytearray(good)
+    struct.pack_into("<I", no_scope, sections[lb.SEC_META][1] + 4 * lb.M_NSCOPES, 0)
+    struct.pack_into("<Q", short_flags, sections[lb.SEC_SCOPE_FLAGS][0] + 16, 4 * n_scopes - 1)
+    for image, words in ((no_scope, "no scope"), (short_flags, "scope flags section too small")):
+        with pytest.raises(engine.HipEngineError) as e:
+            engine.Table(bytes(image))
+        assert words in str(e.value), str(e.value)
+
+
 def test_failing_allocations_and_copies_are_survived():
     """Fault injection on the simulator build: the k-th device / page-locked allocation (or asynchronous copy) from now on fails, for
     k = 0 .. - in the middle of a table load, a one-shot check, the sliced request road with its threads and chained uploads.  Every call then either succeeds or
