@@ -3,6 +3,9 @@
 // The wire walkers take client bytes (integration/go/gpu_cgo.go hands the request over unparsed): every mutated input
 // must either flatten or be refused with an error - never read outside its buffers.
 //   ingest_fuzz <dir> <iterations> <seed>      <dir>: table.blob, messages.bin, offsets.bin, request.bin
+// After the random loop one deterministic pass runs the assembler's write bound (cbi_pb.h action_entry_bound): inputs whose policy
+// key and scope come to the reservation's allowance, one byte either side of it and far past it, on 1 to 64 actions
+// (<dir>: long_messages.bin, long_offsets.bin, long_requests.bin, long_request_offsets.bin, long_scope.bin = the scope index).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -19,6 +22,53 @@ static std::vector<uint8_t> slurp(const std::string& p) {
 }
 static uint64_t rng_state;
 static uint32_t rnd() { rng_state = rng_state * 6364136223846793005ull + 1442695040888963407ull; return (uint32_t)(rng_state >> 33); }
+
+// An exact-size heap copy: a read or write one byte outside it is an ASan error, not a lucky hit on vector slack.
+static uint8_t* exact_copy(const uint8_t* p, size_t n) {
+  uint8_t* e = (uint8_t*)std::malloc(n ? n : 1);
+  if (n) std::memcpy(e, p, n);
+  return e;
+}
+// Results made up for the write-bound pass: every tuple ALLOW, its policy word by turns resource.<kind>... and principal.<id>...
+// at scope `sidx`, its matched scope `sidx`.
+struct LongResult {
+  std::vector<uint8_t> eff, st; std::vector<uint32_t> pol, sc; std::vector<uint64_t> edr; cbh_result res;
+  LongResult(const cbh_batch* v, uint32_t sidx) : eff(v->n_tuples + 1, 1), st(v->n_tuples + 1, 0), pol(v->n_tuples + 1), sc(v->n_tuples + 1, sidx), edr(v->n_requests + 1, 0) {
+    for (size_t k = 0; k < pol.size(); ++k) pol[k] = ((k % 2 ? 3u : 2u) << 28) | sidx;
+    res = cbh_result{eff.data(), pol.data(), sc.data(), st.data(), edr.data()};
+  }
+};
+// -> the number of assemblies done, or -1 (with the library's error printed): nothing here may be refused
+static long write_bound_pass(const cbi_table* t, const std::string& dir) {
+  const auto msgs = slurp(dir + "/long_messages.bin"), offb = slurp(dir + "/long_offsets.bin"), reqs = slurp(dir + "/long_requests.bin"),
+             roffb = slurp(dir + "/long_request_offsets.bin"), scb = slurp(dir + "/long_scope.bin");
+  if (offb.size() < 16 || roffb.size() < 16 || scb.size() != 4) return 0;
+  uint32_t sidx; std::memcpy(&sidx, scb.data(), 4);
+  const uint64_t *off = (const uint64_t*)offb.data(), *roff = (const uint64_t*)roffb.data();
+  const uint32_t n = (uint32_t)(offb.size() / 8 - 1), nr = (uint32_t)(roffb.size() / 8 - 1);
+  long done = 0;
+  for (uint32_t i = 0; i <= n; ++i) {   // each input alone, then (i == n) all of them in one call
+    const uint32_t lo = i < n ? i : 0, cnt = i < n ? 1 : n;
+    std::vector<uint64_t> rel(cnt + 1);
+    for (uint32_t k = 0; k <= cnt; ++k) rel[k] = off[lo + k] - off[lo];
+    uint8_t* exact = exact_copy(msgs.data() + off[lo], rel[cnt]);
+    cbi_batch* b = nullptr; cbi_outputs* o = nullptr;
+    if (cbi_flatten_pb_mt(t, exact, rel.data(), cnt, "default", "", 1, 2, &b)) { std::fprintf(stderr, "write bound, input %u: %s\n", i, cbi_last_error()); return -1; }
+    LongResult r(cbi_batch_view(b), sidx);
+    if (cbi_assemble_pb(t, b, &r.res, exact, rel.data(), cnt, "default", &o)) { std::fprintf(stderr, "write bound, input %u: %s\n", i, cbi_last_error()); return -1; }
+    cbi_outputs_free(o); cbi_batch_free(b); std::free(exact); ++done;
+  }
+  for (uint32_t q = 0; q < nr; ++q) {   // the request form, include_meta set: the response assembler's keys
+    const size_t len = roff[q + 1] - roff[q];
+    uint8_t* exact = exact_copy(reqs.data() + roff[q], len);
+    cbi_batch* b = nullptr; cbi_outputs* o = nullptr;
+    if (cbi_flatten_request_pb(t, exact, len, nullptr, 0, "default", "", 1, 1, &b)) { std::fprintf(stderr, "write bound, request %u: %s\n", q, cbi_last_error()); return -1; }
+    LongResult r(cbi_batch_view(b), sidx);
+    if (cbi_assemble_response_pb(t, b, &r.res, exact, len, "default", &o)) { std::fprintf(stderr, "write bound, request %u: %s\n", q, cbi_last_error()); return -1; }
+    cbi_outputs_free(o); cbi_batch_free(b); std::free(exact); ++done;
+  }
+  return done;
+}
 
 static void mutate(std::vector<uint8_t>& m) {
   const uint32_t kind = rnd() % 8;
@@ -124,7 +174,8 @@ int main(int argc, char** argv) {
     } else ++refused;
     std::free(rexact);
   }
+  const long bound = write_bound_pass(t, dir);
   cbi_table_close(t);
-  std::printf("ok %ld refused %ld\n", ok, refused);
-  return 0;
+  std::printf("ok %ld refused %ld bound %ld\n", ok, refused, bound);
+  return bound < 0 ? 1 : 0;
 }

@@ -51,3 +51,19 @@ def rfc3339_ns(text):
     import datetime
     dt = datetime.datetime.fromisoformat(text.replace("Z", "+00:00"))
     return int(dt.timestamp()) * 1_000_000_000 + dt.microsecond * 1000
+
+
+def long_key_inputs(scope, by_resource):
+    """Inputs whose policy key - "resource.<kind>.v<version>[/scope]", or "principal.<id>.v<version>[/scope]" - comes with the
+    matched scope `scope` to 223 .. 226 bytes (the response assembler allows a key and its scope 224 before it grows its
+    reservation) and to 1000, each with 1, 2, 63 and 64 actions; every second one carries a policy version of its own."""
+    inputs = []
+    for total in (223, 224, 225, 226, 1000):
+        for na in (1, 2, 63, 64):
+            ver = "ver" * 9 if na % 2 else ""
+            rest = ("resource." if by_resource else "principal.") + ".v" + (ver or "default") + ("/" + scope if scope else "") + scope
+            name = "n" * (total - len(rest))
+            inputs.append({"requestId": "w", "actions": ["a%d" % j for j in range(na)],
+                           "principal": {"id": "p" if by_resource else name, "roles": ["employee"], "policyVersion": "" if by_resource else ver},
+                           "resource": {"kind": name if by_resource else "leave_request", "id": "r", "policyVersion": ver if by_resource else ""}})
+    return inputs
