@@ -207,6 +207,7 @@ __device__ __forceinline__ u32 run_uniform_impl(const KernelArgs* ka, const VmLd
         if (r.t == CBH_T_ERR && x.t != CBH_T_ERR && y.t != CBH_T_ERR &&
             (x.t == CBH_T_STRING || x.t == CBH_T_LIST) && x.t == y.t && op == OP_ADD && live)
           L.status |= CBH_ST_UNSUPPORTED;  // concatenation allocates: not on the device
+        if (live && time_window_left(op, x, y, r)) L.status |= CBH_ST_UNSUPPORTED;
         SETTOP(r);
         break;
       }
@@ -484,7 +485,7 @@ __device__ __forceinline__ u32 run_uniform_impl(const KernelArgs* ka, const VmLd
       case OP_TIMESINCE: {
         Val x = TOPV(0); i64 r;
         if (x.t != CBH_T_TIMESTAMP) { FAILTOP1(x, CBH_ERR_NO_SUCH_OVERLOAD); break; }
-        if (__builtin_sub_overflow(c.now_ns, (i64)x.v, &r)) { SETTOP(mk_err()); break; }
+        if (__builtin_sub_overflow(c.now_ns, (i64)x.v, &r)) r = (r >> 63) ^ INT64_MIN;   // Go's Time.Sub saturates (cerbos_lib.go: fn().Sub(ts)); the wrapped difference has the wrong sign
         SETTOP(mk(CBH_T_DURATION, (u64)r));
         break;
       }
@@ -500,7 +501,7 @@ __device__ __forceinline__ u32 run_uniform_impl(const KernelArgs* ka, const VmLd
           const u32 at = zw & 0x3FFFFFFFu;
           const u32 nz = (u32)c.t.theap_val[at];
           const i64 ns = (i64)x.v;
-          const i64 sec = ns >= 0 ? ns / 1000000000ll : -((-ns + 999999999ll) / 1000000000ll);
+          const i64 sec = ns / 1000000000ll - (ns % 1000000000ll < 0);   // the floor (no negation: ns may be INT64_MIN)
           if (nz == 0 || sec < (i64)c.t.theap_val[at + 1] || sec >= 4102444800ll) { if (live) L.status |= CBH_ST_UNSUPPORTED; SETTOP(mk_err()); break; }
           u32 lo = 0, hi = nz;   // entries [lo, hi): from_lo <= sec
           while (hi - lo > 1) { const u32 mid = (lo + hi) / 2; if ((i64)c.t.theap_val[at + 1 + 2 * mid] <= sec) lo = mid; else hi = mid; }

@@ -599,10 +599,11 @@ __device__ inline bool ts_getter(Val x, u32 kind, i64 off_s, i64& out) {
     }
   }
   if (x.t != CBH_T_TIMESTAMP || kind > 9) return false;
-  i64 t;
-  if (__builtin_add_overflow((i64)x.v, off_s * 1000000000ll, &t)) return false;
+  // seconds and nanoseconds first, the zone's offset in seconds then: every instant of the i64 window has an answer in every zone
+  const i64 t = (i64)x.v;
   i64 secs = t / 1000000000ll, nsec = t % 1000000000ll;
   if (nsec < 0) { nsec += 1000000000ll; --secs; }
+  secs += off_s;
   i64 days = secs / 86400, sod = secs % 86400;
   if (sod < 0) { sod += 86400; --days; }
   if (kind >= 6) {
@@ -631,8 +632,15 @@ __device__ inline bool ts_getter(Val x, u32 kind, i64 off_s, i64& out) {
 }
 __device__ __forceinline__ bool dig(u8 ch) { return ch >= '0' && ch <= '9'; }
 
-// RFC 3339 (Go time.Parse(time.RFC3339)): returns 0 ok, 1 parse error, 2 outside the i64-ns range
+// RFC 3339 (Go time.Parse(time.RFC3339)): returns 0 ok, 1 parse error, 2 not decided here: outside the i64-ns range, or one of
+// the forms whose answer in Go's parser this code does not restate - a one-digit hour (Go reads the hour without a fixed width),
+// `,` before the fraction, a zone hour of exactly 24, a zone minute of exactly 60.  They go to the caller's engine.
 __device__ inline int parse_timestamp(gbytes p, u32 n, i64& out_ns) {
+  if (n >= 13 && dig(p[11]) && p[12] == ':') {   // "YYYY-MM-DDTh:": the one-digit hour
+    bool head = p[4] == '-' && p[7] == '-' && p[10] == 'T';
+    for (int i = 0; i < 10; ++i) if (i != 4 && i != 7) head = head && dig(p[i]);
+    if (head) return 2;
+  }
   if (n < 20) return 1;
   for (int i = 0; i < 19; ++i) {
     bool d = dig(p[i]);
@@ -650,10 +658,11 @@ __device__ inline int parse_timestamp(gbytes p, u32 n, i64& out_ns) {
   if (M == 2 && ((Y % 4 == 0 && Y % 100 != 0) || Y % 400 == 0)) dim = 29;
   if (D > dim) return 1;
   u32 i = 19; i64 frac = 0;
+  if (p[i] == ',' && n > 20 && dig(p[20])) return 2;   // Go may take `,` for `.`: not restated, whatever follows
   if (p[i] == '.') {
     ++i; u32 nd = 0;
     while (i < n && dig(p[i])) { if (nd < 9) { frac = frac * 10 + (p[i] - '0'); ++nd; } ++i; }
-    if (nd == 0 && !(i > 20)) return 1;
+    if (i == 20) return 1;   // no digit
     while (nd < 9) { frac *= 10; ++nd; }
   }
   if (i >= n) return 1;
@@ -662,13 +671,18 @@ __device__ inline int parse_timestamp(gbytes p, u32 n, i64& out_ns) {
   else if (p[i] == '+' || p[i] == '-') {
     if (i + 6 != n || !dig(p[i + 1]) || !dig(p[i + 2]) || p[i + 3] != ':' || !dig(p[i + 4]) || !dig(p[i + 5])) return 1;
     u32 oh = (p[i + 1] - '0') * 10 + (p[i + 2] - '0'), om = (p[i + 4] - '0') * 10 + (p[i + 5] - '0');
-    if (oh > 23 || om > 59) return 1;
+    if (oh > 24 || om > 60) return 1;
+    if (oh == 24 || om == 60) return 2;   // Go may accept them: not restated
     off = (i64)(oh * 3600 + om * 60); if (p[i] == '-') off = -off;
   } else return 1;
   i64 secs = days_from_civil(Y, M, D) * 86400 + (i64)(h * 3600 + mi * 60 + s) - off;
   if (secs < -62135596800LL || secs > 253402300799LL) return 1;   // CEL timestamp range
-  if (secs < -9223372036LL || secs > 9223372035LL) return 2;      // not representable in i64 ns
-  out_ns = secs * 1000000000LL + frac;
+  // the i64 window, to the nanosecond: 1677-09-21T00:12:43.145224192Z .. 2262-04-11T23:47:16.854775807Z.  Below zero the sum is
+  // taken from the second above, so that the product itself stays inside
+  i64 f2 = frac;
+  if (secs < 0 && f2 > 0) { ++secs; f2 -= 1000000000LL; }
+  if (secs < -9223372036LL || secs > 9223372036LL) return 2;
+  if (__builtin_add_overflow(secs * 1000000000LL, f2, &out_ns)) return 2;
   return 0;
 }
 
@@ -937,7 +951,7 @@ __device__ inline Val arith(u32 op, Val a, Val b) {
   i64 x = (i64)a.v, y = (i64)b.v, r;
   if (op == OP_ADD) {
     if ((a.t == CBH_T_TIMESTAMP && b.t == CBH_T_DURATION) || (a.t == CBH_T_DURATION && b.t == CBH_T_TIMESTAMP)) {
-      if (__builtin_add_overflow(x, y, &r)) return mk_err();
+      if (__builtin_add_overflow(x, y, &r)) return mk_err();   // a valid timestamp in cel-go, outside the i64 window: the caller flags the lane (time_window_left)
       return mk(CBH_T_TIMESTAMP, (u64)r);
     }
     if (a.t == CBH_T_DURATION && b.t == CBH_T_DURATION) {
@@ -947,12 +961,20 @@ __device__ inline Val arith(u32 op, Val a, Val b) {
   }
   if (op == OP_SUB) {
     if (a.t == CBH_T_TIMESTAMP && b.t == CBH_T_TIMESTAMP) { if (__builtin_sub_overflow(x, y, &r)) return mk_err(); return mk(CBH_T_DURATION, (u64)r); }
-    if (a.t == CBH_T_TIMESTAMP && b.t == CBH_T_DURATION) { if (__builtin_sub_overflow(x, y, &r)) return mk_err(); return mk(CBH_T_TIMESTAMP, (u64)r); }
+    if (a.t == CBH_T_TIMESTAMP && b.t == CBH_T_DURATION) { if (__builtin_sub_overflow(x, y, &r)) return mk_err(); return mk(CBH_T_TIMESTAMP, (u64)r); }   // (as for `+`)
     if (a.t == CBH_T_DURATION && b.t == CBH_T_DURATION) { if (__builtin_sub_overflow(x, y, &r)) return mk_err(); return mk(CBH_T_DURATION, (u64)r); }
   }
   return mk_errc(CBH_ERR_NO_SUCH_OVERLOAD);  // (incl. string/list concatenation: not on the device)
 }
 
+// timestamp + duration, duration + timestamp, timestamp - duration: cel-go adds in seconds against the years 1 .. 9999, and a
+// timestamp of the i64 window with a duration of at most +-292 years lies between 1385 and 2554 - never an error.  Where arith
+// gave one for these operands, the sum left the window: not decided here.
+__device__ __forceinline__ bool time_window_left(u32 op, Val a, Val b, Val r) {
+  return r.t == CBH_T_ERR &&
+         ((a.t == CBH_T_TIMESTAMP && b.t == CBH_T_DURATION && (op == OP_ADD || op == OP_SUB)) ||
+          (a.t == CBH_T_DURATION && b.t == CBH_T_TIMESTAMP && op == OP_ADD));
+}
 
 // comparison / membership operators on two already-loaded values -> bool or error
 __device__ inline Val compare_op(const Ctx& c, Lane& L, u32 op, Val x, Val y) {

@@ -38,14 +38,14 @@ def parse_duration(text):
 def parse_timestamp(text):
     import re
     from datetime import datetime, timedelta, timezone
-    m = re.fullmatch(r"(\d{4})-(\d\d)-(\d\d)[Tt](\d\d):(\d\d):(\d\d)(\.\d+)?([Zz]|[+-]\d\d:\d\d)", text)
+    m = re.fullmatch(r"(\d{4})-(\d\d)-(\d\d)T(\d\d):(\d\d):(\d\d)(\.\d+)?(Z|[+-]\d\d:\d\d)", text, re.ASCII)
     if not m:
         raise FoldError("invalid timestamp")
     y, mo, d, h, mi, sec = (int(m.group(i)) for i in range(1, 7))
     frac = int(((m.group(7) or ".0")[1:] + "000000000")[:9])
     tz = m.group(8)
     off = 0
-    if tz not in ("Z", "z"):
+    if tz != "Z":
         off = (int(tz[1:3]) * 60 + int(tz[4:6])) * (1 if tz[0] == "+" else -1)
     try:
         base = datetime(y, mo, d, h, mi, sec, tzinfo=timezone.utc) - timedelta(minutes=off)
@@ -66,6 +66,14 @@ def format_timestamp(t):
     base = datetime.fromtimestamp(sec, tz=timezone.utc).strftime("%Y-%m-%dT%H:%M:%S")
     frac = ("." + ("%09d" % ns).rstrip("0")) if ns else ""
     return base + frac + "Z"
+
+
+_DUR_MIN, _DUR_MAX = -(1 << 63), (1 << 63) - 1
+
+
+def time_since(now_ns, ts):
+    """conditions/cerbos_lib.go timeSince: now.Sub(ts), and Go's Time.Sub saturates at the largest and smallest Duration"""
+    return Dur(max(_DUR_MIN, min(_DUR_MAX, now_ns - ts)))
 
 
 class _Eval(fold._Eval):
@@ -89,9 +97,9 @@ class _Eval(fold._Eval):
                     return v if isinstance(v, Dur) else parse_duration(fold._need(v, str))
                 if self.now_ns is None:
                     raise NotConst("now")
-                return Dur(self.now_ns - fold._need(v, Ts))
+                return time_since(self.now_ns, fold._need(v, Ts))
         elif name == "timeSince" and not args and self.now_ns is not None:
-            return Dur(self.now_ns - fold._need(self.ev(target, env), Ts))
+            return time_since(self.now_ns, fold._need(self.ev(target, env), Ts))
         return super().call(n, env)
 
     def binop(self, op, a, b):

@@ -18,7 +18,6 @@ Errors are Python exceptions (CelError); ``&&``/``||`` absorb them as CEL requir
 from __future__ import annotations
 
 import base64
-import calendar
 import datetime
 import ipaddress
 import math
@@ -289,40 +288,65 @@ def _chk_ts(ns):
 # ---------------------------------------------------------------- time parsing
 
 _RFC3339 = re.compile(
-    r"^(\d{4})-(\d\d)-(\d\d)[Tt](\d\d):(\d\d):(\d\d)(\.\d+)?([Zz]|[+-]\d\d:\d\d)$")
+    r"^([0-9]{4})-([0-9]{2})-([0-9]{2})T([0-9]{2}):([0-9]{2}):([0-9]{2})(\.[0-9]+)?(Z|[+-][0-9]{2}:[0-9]{2})$")
+_MONTH_DAYS = (31, 28, 31, 30, 31, 30, 31, 31, 30, 31, 30, 31)
+
+
+def _days_from_civil(y, m, d):
+    """days since 1970-01-01 of a date of the proleptic Gregorian calendar, any year (Python's floor division)"""
+    y -= m <= 2
+    era = y // 400
+    yoe = y - era * 400
+    doy = (153 * (m - 3 if m > 2 else m + 9) + 2) // 5 + d - 1
+    return era * 146097 + yoe * 365 + yoe // 4 - yoe // 100 + doy - 719468
+
+
+def _civil_from_days(z):
+    """-> (year, month, day) of a day number, any year"""
+    z += 719468
+    era = z // 146097
+    doe = z - era * 146097
+    yoe = (doe - doe // 1460 + doe // 36524 - doe // 146096) // 365
+    doy = doe - (365 * yoe + yoe // 4 - yoe // 100)
+    mp = (5 * doy + 2) // 153
+    m = mp + 3 if mp < 10 else mp - 9
+    return yoe + era * 400 + (m <= 2), m, doy - (153 * mp + 2) // 5 + 1
 
 
 def parse_timestamp(s: str) -> Timestamp:
+    """Go time.Parse(time.RFC3339, s): `T` and `Z` in upper case only, two digits per field, a second of at most 59."""
     m = _RFC3339.match(s)
-    if not m:
+    if not m or s.endswith("\n"):
         raise CelError("invalid timestamp: %s" % s)
     y, mo, d, h, mi, sec = (int(m.group(i)) for i in range(1, 7))
-    try:
-        datetime.datetime(y, mo, d, h, mi, min(sec, 59))
-    except ValueError:
+    leap = y % 4 == 0 and (y % 100 != 0 or y % 400 == 0)
+    if not (1 <= mo <= 12 and 1 <= d <= _MONTH_DAYS[mo - 1] + (mo == 2 and leap) and h <= 23 and mi <= 59 and sec <= 59):
         raise CelError("invalid timestamp: %s" % s)
     frac = m.group(7)
     ns = int((frac[1:] + "000000000")[:9]) if frac else 0
-    epoch = calendar.timegm((y, mo, d, h, mi, sec, 0, 0, 0))
+    epoch = _days_from_civil(y, mo, d) * 86400 + h * 3600 + mi * 60 + sec
     tz = m.group(8)
-    if tz not in ("Z", "z"):
-        sign = 1 if tz[0] == "+" else -1
-        off = sign * (int(tz[1:3]) * 3600 + int(tz[4:6]) * 60)
-        epoch -= off
+    if tz != "Z":
+        oh, om = int(tz[1:3]), int(tz[4:6])
+        if oh > 23 or om > 59:
+            raise CelError("invalid timestamp: %s" % s)
+        epoch -= (1 if tz[0] == "+" else -1) * (oh * 3600 + om * 60)
     return _chk_ts(epoch * 1_000_000_000 + ns)
 
 
 _DUR_UNITS = {"ns": 1, "us": 1_000, "\u00b5s": 1_000, "\u03bcs": 1_000, "ms": 1_000_000,
               "s": 1_000_000_000, "m": 60_000_000_000, "h": 3_600_000_000_000}
-_DUR_PART = re.compile(r"(\d+(?:\.\d*)?|\.\d+)(ns|us|\u00b5s|\u03bcs|ms|s|m|h)")
+_DUR_PART = re.compile(r"([0-9]*)(?:(\.)([0-9]*))?([^0-9.]+)")
 
 
 def parse_duration(s: str) -> Duration:
-    """Go time.ParseDuration."""
+    """Go time.ParseDuration, step by step: the integer part must stay within 2^63, the digits of a fraction are taken while they fit
+    in 63 bits and are scaled in float64, every group and the running sum must stay within 2^63, and only a negative total may
+    reach it."""
     orig = s
-    sign = 1
-    if s[:1] in "+-":
-        sign = -1 if s[0] == "-" else 1
+    neg = False
+    if s[:1] in ("+", "-"):
+        neg = s[0] == "-"
         s = s[1:]
     if s == "0":
         return Duration(0)
@@ -331,18 +355,27 @@ def parse_duration(s: str) -> Duration:
     pos, total = 0, 0
     while pos < len(s):
         m = _DUR_PART.match(s, pos)
-        if not m:
+        if not m or (not m.group(1) and not m.group(3)) or m.group(4) not in _DUR_UNITS:
             raise CelError("invalid duration: %s" % orig)
-        num, unit = m.group(1), _DUR_UNITS[m.group(2)]
-        if "." in num:
-            ip, fp = num.split(".")
-            total += int(ip or "0") * unit
-            if fp:
-                total += int(fp) * unit // (10 ** len(fp))
-        else:
-            total += int(num) * unit
+        unit = _DUR_UNITS[m.group(4)]
+        v = int(m.group(1) or "0")
+        if v > 1 << 63 or v > (1 << 63) // unit:
+            raise CelError("invalid duration: %s" % orig)
+        v *= unit
+        f, scale = 0, 1.0
+        for ch in m.group(3) or "":
+            if f > ((1 << 63) - 1) // 10 or f * 10 + int(ch) > 1 << 63:
+                break
+            f, scale = f * 10 + int(ch), scale * 10.0
+        if f:
+            v += int(float(f) * (float(unit) / scale))
+            if v > 1 << 63:
+                raise CelError("invalid duration: %s" % orig)
+        total += v
+        if total > 1 << 63:
+            raise CelError("invalid duration: %s" % orig)
         pos = m.end()
-    return _chk_dur(sign * total)
+    return _chk_dur(-total if neg else total)
 
 
 def _tz_offset_seconds(ts: Timestamp, tz):
@@ -357,16 +390,31 @@ def _tz_offset_seconds(ts: Timestamp, tz):
         z = zoneinfo.ZoneInfo(tz)
     except Exception:
         raise CelError("unknown time zone %s" % tz)
-    dt = datetime.datetime.fromtimestamp(ts.ns // 1_000_000_000, tz=z)
+    secs = max(_TS_MIN_S + 2 * 86400, min(_TS_MAX_S - 2 * 86400, ts.ns // 1_000_000_000))      # (datetime's years, with room for the offset)
+    dt = datetime.datetime(1970, 1, 1, tzinfo=datetime.timezone.utc) + datetime.timedelta(seconds=secs)
+    dt = dt.astimezone(z)
     return int(dt.utcoffset().total_seconds())
+
+
+class _Civil:
+    """a broken-down time of any year (datetime stops at the years 1 and 9999; a zone offset moves CEL's first and last day beyond
+    them, and Go answers: year 0 for 0001-01-01T00:00:00Z read in "-12:00")"""
+
+    def __init__(self, secs):
+        self.days, sod = divmod(secs, 86400)
+        self.year, self.month, self.day = _civil_from_days(self.days)
+        self.hour, self.minute, self.second = sod // 3600, sod // 60 % 60, sod % 60
+
+    def weekday(self):           # Monday = 0, as datetime's
+        return (self.days + 3) % 7
+
+    def yday(self):              # 1-based, as time.struct_time's
+        return self.days - _days_from_civil(self.year, 1, 1) + 1
 
 
 def _civil(ts: Timestamp, tz):
     off = _tz_offset_seconds(ts, tz)
-    secs = ts.ns // 1_000_000_000 + off
-    nanos = ts.ns % 1_000_000_000
-    st = datetime.datetime(1970, 1, 1) + datetime.timedelta(seconds=secs)
-    return st, nanos
+    return _Civil(ts.ns // 1_000_000_000 + off), ts.ns % 1_000_000_000
 
 
 # ---------------------------------------------------------------- evaluator
@@ -1115,7 +1163,7 @@ def _f_now(env):
 def _f_time_since(env, ts):
     if not isinstance(ts, Timestamp):
         raise no_such_overload()
-    return _chk_dur(env.now_ns - ts.ns)
+    return Duration(max(INT_MIN, min(INT_MAX, env.now_ns - ts.ns)))     # cerbos_lib.go: fn().Sub(ts) - Go's Time.Sub saturates
 
 
 def _need(v, *types):
@@ -1860,7 +1908,7 @@ _METHODS = {
     "getDate": _ts_getter(lambda st, ns: st.day),
     "getDayOfMonth": _ts_getter(lambda st, ns: st.day - 1),
     "getDayOfWeek": _ts_getter(lambda st, ns: (st.weekday() + 1) % 7),
-    "getDayOfYear": _ts_getter(lambda st, ns: st.timetuple().tm_yday - 1),
+    "getDayOfYear": _ts_getter(lambda st, ns: st.yday() - 1),
     "getHours": _dur_or_ts(lambda ns: _trunc_div(ns, 3_600_000_000_000), lambda st, ns: st.hour),
     "getMinutes": _dur_or_ts(lambda ns: _trunc_div(ns, 60_000_000_000), lambda st, ns: st.minute),
     "getSeconds": _dur_or_ts(lambda ns: _trunc_div(ns, 1_000_000_000), lambda st, ns: st.second),
