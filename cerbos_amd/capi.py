@@ -23,6 +23,7 @@ F_WANT_EFFECTIVE_POLICIES = 8
 CX_DERIVED_ROLES, CX_ACTION_GROUPS = 1, 2        # cbh_cross_upload_ex `accept`
 CX_ALL = CX_DERIVED_ROLES | CX_ACTION_GROUPS
 CX_ROLE_GROUPS = 16                               # ... principals with 5 .. 16 roles (not in CX_ALL: 4 and 8 stay unknown bits)
+RV_PAIRS_FLAGGED, RV_PAIRS_ALLOWED = 1, 2         # cbh_cross_review `pairs`
 
 EFFECT_ALLOW, EFFECT_DENY = 1, 2
 ST_OK, ST_CEL_ERROR, ST_UNSUPPORTED, ST_WANTS_TRACE = 0, 1, 2, 3
@@ -42,6 +43,7 @@ EXPORTED_SYMBOLS = [
     "cbh_table_num_policies", "cbh_table_policy_key", "cbh_check_batch_trail",
     "cbh_batch_upload_cross", "cbh_result_download_allow_bits",
     "cbh_cross_upload", "cbh_cross_check", "cbh_cross_describe", "cbh_cross_release", "cbh_cross_upload_ex", "cbh_cross_pairs_upload",
+    "cbh_cross_review",
 ]
 
 
@@ -67,6 +69,13 @@ class CBatch(C.Structure):
 
 class CParams(C.Structure):
     _fields_ = [("now_ns", C.c_int64), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class CCrossReview(C.Structure):
+    _fields_ = [("pairs", C.c_uint32), ("tile_resources", C.c_uint32), ("pair_actions", C.c_uint64), ("pair_cap", C.c_uint64),
+                ("allow_by_principal", C.c_void_p), ("allow_by_resource", C.c_void_p),
+                ("flagged_by_principal", C.c_void_p), ("flagged_by_resource", C.c_void_p), ("totals", C.c_void_p),
+                ("pair_p", C.c_void_p), ("pair_r", C.c_void_p), ("pair_mask", C.c_void_p), ("n_pairs", C.c_uint64)]
 
 
 class CResult(C.Structure):
@@ -218,6 +227,9 @@ def load():
         lib.cbh_cross_upload_ex.restype = i32
         lib.cbh_cross_pairs_upload.argtypes = [vp, vp, vp, vp, u32, C.POINTER(vp)]
         lib.cbh_cross_pairs_upload.restype = i32
+    if hasattr(lib, "cbh_cross_review"):
+        lib.cbh_cross_review.argtypes = [vp, vp, C.POINTER(CParams), u32, u32, C.POINTER(CCrossReview)]
+        lib.cbh_cross_review.restype = i32
     _lib = lib
     return lib
 
@@ -706,6 +718,14 @@ class DirectFormUnavailable(RuntimeError):
     materialised product (``Table.upload_cross``) instead: same answers, other road."""
 
 
+class CrossReview:
+    """What ``CrossSet.review`` returns: numpy arrays in the set's DEVICE orders (``cross.review_counts`` gives the caller's), or None
+    where something was not asked for."""
+    allow_by_principal = allow_by_resource = flagged_by_principal = flagged_by_resource = totals = None
+    pair_p = pair_r = pair_mask = None
+    n_pairs = 0
+
+
 class CrossSet:
     """A set of ``cbh_cross_upload``: N principals x M resources x A actions, decided tile by tile from the N + M rows."""
 
@@ -749,6 +769,53 @@ class CrossSet:
         _check(load().cbh_cross_pairs_upload(self.table.h, self.h, pp.ctypes.data if pp.size else None, pr.ctypes.data if pr.size else None,
                                              pp.size, C.byref(h)))
         return DeviceBatch(self.table, h, int(pp.size) * self.shape[2], int(pp.size))
+
+    def review(self, r_begin, r_end, flags=0, now_ns=0, want_flagged=False, pairs=None, pair_actions=None, pair_cap=None, tile_resources=0):
+        """``cbh_cross_review`` -> ``CrossReview``: the planes of ``check(r_begin, r_end, want_flagged=True)`` reduced on the device,
+        in DEVICE order - ``allow_by_principal`` uint32[a][n], ``allow_by_resource`` uint32[a][r_end - r_begin], ``flagged_*`` the
+        same (with ``want_flagged``, else None), ``totals`` uint64[2][a] (allow, flagged).  ``pairs``: None, "flagged" or "allowed" -
+        the pairs with such an action among ``pair_actions`` (an iterable of action indices or a mask; None = all) as ``pair_p``,
+        ``pair_r``, ``pair_mask`` in ascending (pair_r, pair_p), what ``pairs_batch`` takes; ``n_pairs`` = how many there are.
+        ``pair_cap``: None = ask for the count first and call again with exactly that many entries; a number = one call, a list of
+        at most that many entries (``n_pairs`` may be larger).  ``tile_resources``: resources per internal tile, 0 = the library's
+        choice."""
+        n, m, a = self.shape
+        kind = {None: 0, "flagged": RV_PAIRS_FLAGGED, "allowed": RV_PAIRS_ALLOWED}.get(pairs, pairs)
+        if pair_actions is None:
+            sel = 0
+        elif isinstance(pair_actions, (int, np.integer)):
+            sel = int(pair_actions)
+        else:
+            sel = sum(1 << int(k) for k in set(pair_actions))
+        mr = max(r_end - r_begin, 0)
+        p = CParams(now_ns, flags, 0)
+
+        def call(cap, counts=True):
+            out = CrossReview()
+            if counts:
+                out.allow_by_principal, out.allow_by_resource = np.zeros((a, n), dtype=np.uint32), np.zeros((a, mr), dtype=np.uint32)
+                if want_flagged:
+                    out.flagged_by_principal, out.flagged_by_resource = np.zeros((a, n), dtype=np.uint32), np.zeros((a, mr), dtype=np.uint32)
+                out.totals = np.zeros((2, a), dtype=np.uint64)
+            if kind:
+                out.pair_p, out.pair_r, out.pair_mask = np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint32), np.zeros(cap, dtype=np.uint64)
+            ptr = lambda x: x.ctypes.data if x is not None and x.size else None
+            rv = CCrossReview(kind, tile_resources, sel, cap, ptr(out.allow_by_principal), ptr(out.allow_by_resource), ptr(out.flagged_by_principal),
+                              ptr(out.flagged_by_resource), ptr(out.totals), ptr(out.pair_p), ptr(out.pair_r), ptr(out.pair_mask), 0)
+            rc = load().cbh_cross_review(self.table.h, self.h, C.byref(p), r_begin, r_end, C.byref(rv))
+            if rc == 1:
+                raise DirectFormUnavailable(load().cbh_last_error().decode("utf-8", "replace"))
+            if rc != 2:
+                _check(rc)
+            out.n_pairs = int(rv.n_pairs)
+            if kind:
+                k = min(out.n_pairs, cap)
+                out.pair_p, out.pair_r, out.pair_mask = out.pair_p[:k], out.pair_r[:k], out.pair_mask[:k]
+            return out
+
+        if kind and pair_cap is None:      # the number of pairs alone (no count is reduced for it), then everything with exactly that cap
+            return call(call(0, counts=False).n_pairs)
+        return call(0 if pair_cap is None else int(pair_cap))
 
     def describe(self, flags=0):
         """The kernel a ``check`` with these flags would launch (``cbh_cross_describe``), or "none: ..." ."""

@@ -167,6 +167,38 @@ def flagged_pairs(cross_set, r_begin, r_end, flagged):
     return (q % n).astype(np.uint32), (r_begin + q // n).astype(np.uint32), mask
 
 
+def review_counts(cross_set, r_begin, r_end, result):
+    """``capi.CrossSet.review(r_begin, r_end, ...)`` -> the same in the CALLER's orders, as ``allow_cube_planes`` gives cubes: a
+    namespace with ``allow_by_principal`` / ``flagged_by_principal`` uint32[n][a] - row i = principals[i] -, ``allow_by_resource`` /
+    ``flagged_by_resource`` uint32[r_end - r_begin][a] - row j = the j-th of the tile's resources taken in the caller's resource
+    order (the tile holds resources ``r_order[r_begin:r_end]``) -, ``totals`` as they are, and the pairs as (``pair_p``, ``pair_r``)
+    = indices into the caller's principals and resources, in the list's order, with ``pair_mask`` and ``n_pairs``.  What the review
+    did not return stays None."""
+    from types import SimpleNamespace
+    po, ro = np.asarray(cross_set.p_order), np.asarray(cross_set.r_order)
+    rank = np.argsort(np.argsort(ro[r_begin:r_end]))          # device position within the tile -> place in the caller's order
+
+    def by_principal(x):
+        if x is None:
+            return None
+        out = np.empty((x.shape[1], x.shape[0]), dtype=x.dtype)
+        out[po] = x.T
+        return out
+
+    def by_resource(x):
+        if x is None:
+            return None
+        out = np.empty((x.shape[1], x.shape[0]), dtype=x.dtype)
+        out[rank] = x.T
+        return out
+
+    return SimpleNamespace(
+        allow_by_principal=by_principal(result.allow_by_principal), flagged_by_principal=by_principal(result.flagged_by_principal),
+        allow_by_resource=by_resource(result.allow_by_resource), flagged_by_resource=by_resource(result.flagged_by_resource),
+        totals=result.totals, n_pairs=result.n_pairs, pair_mask=result.pair_mask,
+        pair_p=None if result.pair_p is None else po[result.pair_p], pair_r=None if result.pair_r is None else ro[result.pair_r])
+
+
 def allow_cube(batch, bits):
     """``capi.Table.download_allow_bits`` of the batch -> bool[n][m][a]: [i][j][k] = principals[i] may actions[k] on resources[j]."""
     n, m, a = batch.shape

@@ -1,5 +1,5 @@
 // Host side of libcerbos_hip.so, part 3 of 5 (included by cbh_engine.hip, host pass only, behind cbh_host_resident.h, whose plan_for, batch constructor and
-// makers' tail it uses): the cross road - N x M x A from N + M halves, as a materialised product, as a direct set, as a batch of chosen pairs of a set.
+// makers' tail it uses): the cross road - N x M x A from N + M halves, as a materialised product, as a direct set - checked tile by tile or reviewed range by range -, as a batch of chosen pairs of a set.
 #pragma once
 
 // ---- cross-product batches: N + M halves up, the N x M product built in device memory (cbh_cross.h) ------------------------
@@ -241,37 +241,41 @@ extern "C" int cbh_cross_upload_ex(cbh_table* t, uint32_t device_index, const cb
 extern "C" int cbh_cross_upload(cbh_table* t, uint32_t device_index, const cbh_batch* halves, const cbh_cross* x, cbh_cross_set** out) {
   return cbh_cross_upload_ex(t, device_index, halves, x, 0, out);
 }
-static int cross_set_check(cbh_table* t, cbh_cross_set* cs, const cbh_params* p, uint32_t r_begin, uint32_t r_end, uint64_t* allow, uint64_t* flagged, size_t words_per_plane) {
-  if (!t || !cs || !p || !allow) return fail("null argument");
+// What cbh_cross_check and cbh_cross_review refuse alike, under the caller's name: null handles, a set of another table, a range
+// that is empty or ends behind the set's resources.
+static int cross_call_args(cbh_table* t, cbh_cross_set* cs, const cbh_params* p, uint32_t r_begin, uint32_t r_end, const char* who) {
+  if (!t || !cs || !p) return fail("null argument");
+  if (cs->b->table != t) return fail("the set was uploaded for a different table");
+  if (r_begin >= r_end || r_end > cs->m) return fail(std::string(who) + ": [r_begin, r_end) must be a non-empty range of the set's resources");
+  return 0;
+}
+// The set's plane block holds `need` words (called with the replica's lock held): a larger tile than any before gets a new block,
+// and the old one goes back to the replica's pool (every check and review ends with a wait for its copies, so nothing of the stream
+// still reads it).
+static int cross_planes_reserve(cbh_cross_set* cs, size_t need) {
+  if (need <= cs->plane_cap) return 0;
   cbh_device_batch* b = cs->b;
-  if (b->table != t) return fail("the set was uploaded for a different table");
-  if (r_begin >= r_end || r_end > cs->m) return fail("cbh_cross_check: [r_begin, r_end) must be a non-empty range of the set's resources");
-  const u64 nt = (u64)cs->n * (r_end - r_begin);
-  if (nt >= (1ull << 32)) return fail("cbh_cross_check: the tile has 2^32 requests or more: take fewer resources");
-  const size_t W = (size_t)((nt + 63) / 64);
-  if (words_per_plane < W) return fail("cbh_cross_check: words_per_plane is less than (n_principals * (r_end - r_begin) + 63) / 64");
-  CbhPlan pl;
-  const cbh_cross_kernel_fn fn = cross_kernel_for(cs, p->flags, pl);
-  if (!fn) { g_err = "cbh_cross_check: these flags choose a plan without a direct form"; return 1; }
   Replica* rep = b->rep;
-  std::lock_guard<std::mutex> lk(rep->mu);
-  HIPCHK(hipSetDevice(rep->device));
-  hipStream_t s = b->stream;
-  const size_t per = (size_t)cs->a * W, need = per * (flagged ? 2 : 1);
-  if (need > cs->plane_cap) {
-    // a larger tile than any before: a new block, and the old one back to the replica's pool (every check ends with a wait for its
-    // copies, so nothing of the stream still reads it)
-    u64* np = nullptr;
-    if (dalloc(b, np, need) != 0) return -1;
-    if (cs->planes) {
-      for (size_t i = 0; i < b->allocs.size(); ++i) if (b->allocs[i].first == (void*)cs->planes) {
-        { std::lock_guard<std::mutex> pl(rep->pool_mu); rep->pool_free.push_back(b->allocs[i]); }
-        b->allocs[i] = b->allocs.back(); b->allocs.pop_back();
-        break;
-      }
+  u64* np = nullptr;
+  if (dalloc(b, np, need) != 0) return -1;
+  if (cs->planes) {
+    for (size_t i = 0; i < b->allocs.size(); ++i) if (b->allocs[i].first == (void*)cs->planes) {
+      { std::lock_guard<std::mutex> pl(rep->pool_mu); rep->pool_free.push_back(b->allocs[i]); }
+      b->allocs[i] = b->allocs.back(); b->allocs.pop_back();
+      break;
     }
-    cs->planes = np; cs->plane_cap = need;
   }
+  cs->planes = np; cs->plane_cap = need;
+  return 0;
+}
+// The launches that decide the tile [r_begin, r_end) into the set's plane block, [allow | flagged][a][W], on the set's stream: the
+// one loop of cbh_cross_check and cbh_cross_review (the block holds the tile: cross_planes_reserve).
+static int cross_launch_tile(cbh_cross_set* cs, const cbh_params* p, cbh_cross_kernel_fn fn, const CbhPlan& pl, uint32_t r_begin, uint32_t r_end, bool flagged) {
+  cbh_device_batch* b = cs->b;
+  Replica* rep = b->rep;
+  hipStream_t s = b->stream;
+  const u64 nt = (u64)cs->n * (r_end - r_begin);
+  const size_t W = (size_t)((nt + 63) / 64), per = (size_t)cs->a * W;
   KernelArgs ka;
   std::memset(&ka, 0, sizeof(ka));
   ka.t = rep->dev; ka.b = b->dev; ka.now_ns = p->now_ns;
@@ -293,6 +297,26 @@ static int cross_set_check(cbh_table* t, cbh_cross_set* cs, const cbh_params* p,
     }
   }
   HIPCHK(hipGetLastError());
+  return 0;
+}
+static int cross_set_check(cbh_table* t, cbh_cross_set* cs, const cbh_params* p, uint32_t r_begin, uint32_t r_end, uint64_t* allow, uint64_t* flagged, size_t words_per_plane) {
+  if (!allow) return fail("null argument");
+  if (cross_call_args(t, cs, p, r_begin, r_end, "cbh_cross_check") != 0) return -1;
+  cbh_device_batch* b = cs->b;
+  const u64 nt = (u64)cs->n * (r_end - r_begin);
+  if (nt >= (1ull << 32)) return fail("cbh_cross_check: the tile has 2^32 requests or more: take fewer resources");
+  const size_t W = (size_t)((nt + 63) / 64);
+  if (words_per_plane < W) return fail("cbh_cross_check: words_per_plane is less than (n_principals * (r_end - r_begin) + 63) / 64");
+  CbhPlan pl;
+  const cbh_cross_kernel_fn fn = cross_kernel_for(cs, p->flags, pl);
+  if (!fn) { g_err = "cbh_cross_check: these flags choose a plan without a direct form"; return 1; }
+  Replica* rep = b->rep;
+  std::lock_guard<std::mutex> lk(rep->mu);
+  HIPCHK(hipSetDevice(rep->device));
+  hipStream_t s = b->stream;
+  const size_t per = (size_t)cs->a * W;
+  if (cross_planes_reserve(cs, per * (flagged ? 2 : 1)) != 0) return -1;
+  if (cross_launch_tile(cs, p, fn, pl, r_begin, r_end, flagged != nullptr) != 0) return -1;
   for (int which = 0; which < (flagged ? 2 : 1); ++which) {
     uint64_t* dst = which ? flagged : allow; const u64* src = cs->planes + (size_t)which * per;
     if (words_per_plane == W) HIPCHK(hipMemcpyAsync(dst, src, per * 8, hipMemcpyDeviceToHost, s));
@@ -303,6 +327,133 @@ static int cross_set_check(cbh_table* t, cbh_cross_set* cs, const cbh_params* p,
 }
 extern "C" int cbh_cross_check(cbh_table* t, cbh_cross_set* cs, const cbh_params* p, uint32_t r_begin, uint32_t r_end, uint64_t* allow, uint64_t* flagged, size_t words_per_plane) {
   try { return cross_set_check(t, cs, p, r_begin, r_end, allow, flagged, words_per_plane); } catch (...) { return fail("out of memory"); }
+}
+
+// ---- the review of a set: a range of resources decided tile by tile, every tile's planes reduced on the device (cbh_cross.h) ----
+// The launches per tile are cbh_cross_check's (cross_launch_tile) into the set's own plane block, which is reused from tile to tile;
+// behind them the review kernels read the planes and add to counters that live for the call.  No plane is copied to the host.
+// Tile rule: the caller's tile_resources, else the largest count of resources whose planes - [kinds][A][words], kinds = 2 where
+// anything flagged is asked for - fit CBH_CROSS_REVIEW_PLANE_BYTES; in either case fewer than 2^32 requests, and at least one resource.
+static const size_t CBH_CROSS_REVIEW_PLANE_BYTES = (size_t)256 << 20;
+static const u32 CBH_CROSS_REVIEW_MAX_GRID = 8192;   // workgroups of a rows / columns launch: the kernels stride over the rest
+// The device blocks a review takes from the replica's pool, behind `mark` in the set's batch: back to the pool when the call ends,
+// however it ends - after a wait for whatever of the stream may still use them.
+struct CrossScratch {
+  cbh_device_batch* b; size_t mark; bool idle;
+  ~CrossScratch() {
+    if (!idle && hipStreamSynchronize(b->stream) != hipSuccess) (void)hipGetLastError();
+    std::lock_guard<std::mutex> pl(b->rep->pool_mu);
+    while (b->allocs.size() > mark) { b->rep->pool_free.push_back(b->allocs.back()); b->allocs.pop_back(); }
+  }
+};
+static u32 bit_length(u64 v) { u32 n = 0; while (v) { ++n; v >>= 1; } return n; }
+static int cross_set_review(cbh_table* t, cbh_cross_set* cs, const cbh_params* p, uint32_t r_begin, uint32_t r_end, struct cbh_cross_review* rv) {
+  if (!rv) return fail("null argument");
+  if (cross_call_args(t, cs, p, r_begin, r_end, "cbh_cross_review") != 0) return -1;
+  const u32 N = cs->n, A = cs->a, mr = r_end - r_begin;
+  if (rv->pairs != 0 && rv->pairs != CBH_RV_PAIRS_FLAGGED && rv->pairs != CBH_RV_PAIRS_ALLOWED) return fail("cbh_cross_review: `pairs` must be 0, CBH_RV_PAIRS_FLAGGED or CBH_RV_PAIRS_ALLOWED");
+  if (A < 64u && (rv->pair_actions >> A) != 0) return fail("cbh_cross_review: `pair_actions` has a bit of an action the set does not have");
+  if (rv->pairs && rv->pair_cap && (!rv->pair_p || !rv->pair_r || !rv->pair_mask)) return fail("cbh_cross_review: pair_cap entries are asked for, and pair_p, pair_r or pair_mask is NULL");
+  CbhPlan pl;
+  const cbh_cross_kernel_fn fn = cross_kernel_for(cs, p->flags, pl);
+  if (!fn) { g_err = "cbh_cross_review: these flags choose a plan without a direct form"; return 1; }
+  const bool want_p = rv->allow_by_principal || rv->flagged_by_principal;
+  const bool want_r = rv->allow_by_resource || rv->flagged_by_resource || rv->totals;   // (the totals are the sums of the per-resource counts)
+  const bool want_f = rv->flagged_by_principal || rv->flagged_by_resource || rv->totals || rv->pairs == CBH_RV_PAIRS_FLAGGED;
+  const u32 kinds = want_f ? 2u : 1u;
+  const size_t n_planes = (size_t)kinds * A;
+  // the tile
+  u64 mt = rv->tile_resources;
+  if (!mt) mt = (u64)(CBH_CROSS_REVIEW_PLANE_BYTES / 8 / n_planes) * 64u / N;   // (N * mt bits in that many words)
+  mt = std::min(std::max<u64>(mt, 1), std::min<u64>(((1ull << 32) - 1u) / N, mr));
+  const size_t W_max = (size_t)(((u64)N * mt + 63) / 64);
+  const u64 sel = rv->pair_actions ? rv->pair_actions : (A < 64u ? (1ull << A) - 1ull : ~0ull);
+  cbh_device_batch* b = cs->b;
+  Replica* rep = b->rep;
+  std::lock_guard<std::mutex> lk(rep->mu);
+  HIPCHK(hipSetDevice(rep->device));
+  hipStream_t s = b->stream;
+  if (cross_planes_reserve(cs, n_planes * W_max) != 0) return -1;
+  CrossScratch scratch{b, b->allocs.size(), false};
+  u32* d_by_p = nullptr; u32* d_by_r = nullptr; u64* d_tot = nullptr;
+  u32* d_wavesum = nullptr; u64* d_state = nullptr; u32* d_pp = nullptr; u32* d_pr = nullptr; u64* d_pm = nullptr;
+  const u64 cap = rv->pairs ? std::min<u64>(rv->pair_cap, (u64)N * mr) : 0;
+  if (want_p) {   // accumulated over the tiles: zeroed on the stream
+    if (dalloc(b, d_by_p, n_planes * N) != 0) return -1;
+    HIPCHK(hipMemsetAsync(d_by_p, 0, n_planes * N * 4, s));
+  }
+  if (want_r && dalloc(b, d_by_r, n_planes * mr) != 0) return -1;   // (every count is written once, by its tile)
+  if (rv->totals && dalloc(b, d_tot, (size_t)2 * A) != 0) return -1;
+  if (rv->pairs) {
+    if (dalloc(b, d_wavesum, (W_max + 63) / 64) != 0 || dalloc(b, d_state, 2) != 0) return -1;
+    HIPCHK(hipMemsetAsync(d_state, 0, 16, s));
+    if (cap && (dalloc(b, d_pp, (size_t)cap) != 0 || dalloc(b, d_pr, (size_t)cap) != 0 || dalloc(b, d_pm, (size_t)cap) != 0)) return -1;
+  }
+  for (u64 lo = r_begin; lo < r_end; lo += mt) {
+    const u32 hi = (u32)std::min<u64>(lo + mt, r_end), m = hi - (u32)lo;
+    if (cross_launch_tile(cs, p, fn, pl, (u32)lo, hi, want_f) != 0) return -1;
+    const u32 W = (u32)(((u64)N * m + 63) / 64);
+    CrossReviewArgs ra{};
+    ra.planes = cs->planes; ra.by_r = d_by_r; ra.by_p = d_by_p;
+    ra.n = N; ra.mt = m; ra.a = A; ra.kinds = kinds; ra.words = W; ra.mr = mr; ra.j0 = (u32)lo - r_begin;
+    if (want_r) {
+      // as many lanes to a resource as it has words, up to a wave; a lane counts at most the bits of its share of the words, and of the resource
+      const u32 wpr = (N + 63u) / 64u;
+      ra.g = 1; while (ra.g * 2u <= std::min(wpr, 64u)) ra.g *= 2u;
+      ra.bits = bit_length(std::min<u64>(N, 64ull * ((wpr + 1u + ra.g - 1u) / ra.g)));
+      const u64 blocks = ((u64)n_planes * m + 256u / ra.g - 1u) / (256u / ra.g);
+      ra.grid = (u32)std::min<u64>(blocks, CBH_CROSS_REVIEW_MAX_GRID);
+      hipLaunchKernelGGL(cbh_cross_review_rows_kernel, dim3(ra.grid), dim3(256), 0, s, ra);
+    }
+    if (want_p) {
+      // strips long enough that a destination gets few atomics, short enough that the launch has some 32 K waves; 16 .. 256 resources
+      const u64 per_strip = (u64)n_planes * ((N + 63u) / 64u);
+      const u32 strips_wanted = (u32)std::max<u64>(1, 32768u / per_strip);
+      ra.strip = std::min(std::max((m + strips_wanted - 1u) / strips_wanted, 16u), 256u);
+      const u64 blocks = (per_strip * ((m + ra.strip - 1u) / ra.strip) + 3u) / 4u;
+      ra.grid = (u32)std::min<u64>(blocks, CBH_CROSS_REVIEW_MAX_GRID);
+      hipLaunchKernelGGL(cbh_cross_review_cols_kernel, dim3(ra.grid), dim3(256), 0, s, ra);
+    }
+    if (rv->pairs) {
+      CrossPairArgs pa{};
+      pa.planes = cs->planes + (rv->pairs == CBH_RV_PAIRS_FLAGGED ? (size_t)A * W : 0);
+      pa.wavesum = d_wavesum; pa.state = d_state; pa.pair_p = d_pp; pa.pair_r = d_pr; pa.pair_mask = d_pm;
+      pa.sel = sel; pa.cap = cap; pa.n = N; pa.a = A; pa.words = W; pa.r0 = (u32)lo;
+      hipLaunchKernelGGL(cbh_cross_review_pair_count_kernel, dim3((W + 255u) / 256u), dim3(256), 0, s, pa);
+      hipLaunchKernelGGL(cbh_cross_review_pair_scan_kernel, dim3(1), dim3(64), 0, s, pa);
+      if (cap) hipLaunchKernelGGL(cbh_cross_review_pair_scatter_kernel, dim3((W + 255u) / 256u), dim3(256), 0, s, pa);
+    }
+    HIPCHK(hipGetLastError());
+  }
+  if (rv->totals) {
+    CrossTotalsArgs ta{d_by_r, d_tot, mr, bit_length((u64)((mr + 63u) / 64u) * N)};
+    hipLaunchKernelGGL(cbh_cross_review_totals_kernel, dim3(2u * A), dim3(64), 0, s, ta);
+    HIPCHK(hipGetLastError());
+  }
+  // one copy per wanted output, one wait (and, where a list is wanted, its entries - as many as there are - and a second wait)
+  const size_t by_p = (size_t)A * N * 4, by_r = (size_t)A * mr * 4;
+  if (rv->allow_by_principal) HIPCHK(hipMemcpyAsync(rv->allow_by_principal, d_by_p, by_p, hipMemcpyDeviceToHost, s));
+  if (rv->flagged_by_principal) HIPCHK(hipMemcpyAsync(rv->flagged_by_principal, d_by_p + (size_t)A * N, by_p, hipMemcpyDeviceToHost, s));
+  if (rv->allow_by_resource) HIPCHK(hipMemcpyAsync(rv->allow_by_resource, d_by_r, by_r, hipMemcpyDeviceToHost, s));
+  if (rv->flagged_by_resource) HIPCHK(hipMemcpyAsync(rv->flagged_by_resource, d_by_r + (size_t)A * mr, by_r, hipMemcpyDeviceToHost, s));
+  if (rv->totals) HIPCHK(hipMemcpyAsync(rv->totals, d_tot, (size_t)2 * A * 8, hipMemcpyDeviceToHost, s));
+  u64 n_pairs = 0;
+  if (rv->pairs) HIPCHK(hipMemcpyAsync(&n_pairs, d_state, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  const size_t n_out = (size_t)std::min(n_pairs, cap);
+  if (n_out) {
+    HIPCHK(hipMemcpyAsync(rv->pair_p, d_pp, n_out * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(rv->pair_r, d_pr, n_out * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(rv->pair_mask, d_pm, n_out * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+  }
+  scratch.idle = true;
+  rv->n_pairs = n_pairs;
+  if (n_pairs > rv->pair_cap) { g_err = "cbh_cross_review: pair_cap is smaller than the number of pairs (n_pairs says how many)"; return 2; }
+  return 0;
+}
+extern "C" int cbh_cross_review(cbh_table* t, cbh_cross_set* cs, const cbh_params* p, uint32_t r_begin, uint32_t r_end, struct cbh_cross_review* rv) {
+  try { return cross_set_review(t, cs, p, r_begin, r_end, rv); } catch (...) { return fail("out of memory"); }
 }
 extern "C" const char* cbh_cross_describe(cbh_table* t, cbh_cross_set* cs, const cbh_params* p) {
   static thread_local std::string s;

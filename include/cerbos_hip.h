@@ -386,6 +386,56 @@ void cbh_cross_release(cbh_cross_set* set);
 int cbh_cross_pairs_upload(cbh_table* t, cbh_cross_set* set, const uint32_t* pair_p, const uint32_t* pair_r, uint32_t n_pairs,
                            cbh_device_batch** out);
 
+/* ---- The review of a set: counts and pair lists reduced on the device, no plane crosses the host link -------------
+ * An access review does not ask for the bits: it asks how many resources each principal may act on, how many principals each
+ * resource lets in, which pairs are allowed an action, and which pairs are flagged and have to go to another road.
+ * cbh_cross_review decides the resources [r_begin, r_end) of a set exactly as cbh_cross_check would - the same kernels, flags and
+ * launches per group of actions and of roles - in tiles it chooses itself, and reduces every tile's planes ON THE DEVICE; only the
+ * summaries come back.  N * (r_end - r_begin) is not bounded: the library takes tiles of fewer than 2^32 requests - the caller's
+ * `tile_resources` per tile (clamped to that bound and to the range), else the largest count of resources whose planes fit a fixed
+ * budget of device memory, 256 MiB (CBH_CROSS_REVIEW_PLANE_BYTES in cerbos_amd/csrc/cbh_host_cross.h), and at least one.  The plane
+ * block is the set's own, the one cbh_cross_check uses, reused from tile to tile; the counters live in device memory for the call.
+ *
+ * Definition.  Every output is the reduction of the planes that cbh_cross_check(..., allow, flagged, ...) returns for the same set,
+ * flags and resources, bit for bit - including the note above that the `allow` bit of a flagged tuple is 0.  With k an action,
+ * i' a principal and j' a resource in the set's DEVICE orders, as in the planes:
+ *   allow_by_principal[k * N + i']              the resources of the range on which principal i' is allowed action k
+ *   allow_by_resource[k * (r_end - r_begin) + j]   the principals allowed action k on resource r_begin + j
+ *   flagged_by_principal, flagged_by_resource   the same counts of the `flagged` planes
+ *   totals[k], totals[A + k]                    the set bits of action k's `allow` plane, of its `flagged` plane, over the range
+ *   pair_p, pair_r, pair_mask                   with `pairs` = CBH_RV_PAIRS_FLAGGED (CBH_RV_PAIRS_ALLOWED): the pairs (i', j') of the range
+ *                                               with a flagged (allowed) action among `pair_actions`, in ascending (pair_r, pair_p) -
+ *                                               the ascending bit index of the planes -, and per pair a word whose bit k = action k
+ *                                               of the pair is flagged (allowed), for ALL k < A, selected or not.  pair_p and pair_r are
+ *                                               what cbh_cross_pairs_upload takes, unchanged.
+ * Every out pointer may be NULL: not wanted.  `pair_actions`: bit k = action k takes part in the selection; 0 = all A actions.
+ * Returns 0 = done; 1 = these flags choose a plan without a direct form, as for cbh_cross_check, nothing is written; 2 = `pair_cap`
+ * is too small: the counts are complete, the first pair_cap pairs are written, n_pairs holds the number needed (the `need`
+ * convention of cbh_wire_outputs) - `pairs` != 0 with pair_cap = 0 is the way to ask for n_pairs alone, and returns 2 when there are
+ * pairs; entries behind min(n_pairs, pair_cap) are not written.  < 0 = an error with a cbh_last_error text: a null t, set, p or rv,
+ * a set of another table, an empty range, r_end > M, a value of `pairs` other than 0 or exactly one of CBH_RV_PAIRS_*, a bit of
+ * `pair_actions` at or above A, `pairs` != 0 with pair_cap > 0 and a null list pointer, a failed allocation or copy.  Nothing is
+ * written for a refused argument; the set stays usable after a failure.  Calls on one set queue in call order with cbh_cross_check;
+ * cbh_cross_check, its planes and every other entry point behave exactly as before. */
+#define CBH_HAS_CROSS_REVIEW 1
+#define CBH_RV_PAIRS_FLAGGED 1u  /* list the pairs with a flagged action among pair_actions; pair_mask = their flagged actions */
+#define CBH_RV_PAIRS_ALLOWED 2u  /* list the pairs with an allowed action among pair_actions; pair_mask = their allowed actions */
+struct cbh_cross_review {   /* (the tag only: the name without `struct` is the function's) */
+  uint32_t pairs;           /* 0 = no list, or exactly one of CBH_RV_PAIRS_*; any other value is refused */
+  uint32_t tile_resources;  /* 0 = the library's choice; else resources per internal tile (a memory budget; the tests) */
+  uint64_t pair_actions;    /* bit k = action k takes part in the selection; 0 = all A actions; a bit >= A is refused */
+  uint64_t pair_cap;        /* entries in pair_p / pair_r / pair_mask */
+  /* out; every pointer may be NULL = not wanted.  Indices are the set's DEVICE orders, as in the planes. */
+  uint32_t* allow_by_principal;    /* [A][N]: resources of the range on which principal i' is allowed action k */
+  uint32_t* allow_by_resource;     /* [A][r_end - r_begin]: principals allowed action k on resource r_begin + j */
+  uint32_t* flagged_by_principal;  /* [A][N] */
+  uint32_t* flagged_by_resource;   /* [A][r_end - r_begin] */
+  uint64_t* totals;                /* [2][A]: allow, flagged */
+  uint32_t* pair_p; uint32_t* pair_r; uint64_t* pair_mask;  /* [pair_cap]; ascending (pair_r, pair_p) = ascending bit index */
+  uint64_t n_pairs;                /* out: pairs selected in the range, also when that is more than pair_cap */
+};
+int cbh_cross_review(cbh_table* t, cbh_cross_set* set, const cbh_params* p, uint32_t r_begin, uint32_t r_end, struct cbh_cross_review* rv);
+
 /* ---- Device-side ingest: serialized CheckInputs in, a resident batch out (the GPU flattens) ----------------------
  * The reference decodes each CheckInput and builds its request view on the CPU (internal/ruletable/check.go:536-554); so did
  * libcerbos_ingest.so (cbi_flatten_pb).  cbh_wire_flatten uploads the raw messages - `bytes`, message i =

@@ -36,6 +36,14 @@ same, so it must not differ).
   python tools/cross_bench.py --pairs c3:4096:1024:65536
                                                    CrossSet.pairs_batch of that many random pairs, wall clock (under rocprofv3
                                                    --kernel-trace --stats: the device time of cbh_cross_gather_kernel)
+  python tools/cross_bench.py --review c2:4096:1024
+                                                   what a review costs, inputs resident, four bodies ALTERNATING in one process, wall
+                                                   clock in ms: (a) check with both kinds of planes + the numpy reduction to counts +
+                                                   cross.flagged_pairs - what a caller did before cbh_cross_review; (b) that check
+                                                   alone; (c) CrossSet.review, every count, no list; (d) review with the flagged list, in one call (pair_cap = twice the list's length).
+                                                   C3 runs under F_WANT_DERIVED_ROLES (its flagged list is not empty)
+  python tools/cross_bench.py --profile-review c2:4096:1024
+                                                   body (c) three times and nothing else, for rocprofv3 --kernel-trace --stats
 One JSON line per configuration on stdout."""
 import argparse
 import json
@@ -173,6 +181,31 @@ def timed_alternating(table, reps, warmup, bodies):
     return out
 
 
+def review_bodies(cs, n, m, a, flags, cap):
+    """(a) .. (d) of --review; each returns None (nothing to close)"""
+    def reduce_on_host():
+        allow, flagged = cs.check(0, m, flags=flags, now_ns=NOW, want_flagged=True)
+        for planes in (allow, flagged):
+            by = np.ascontiguousarray(planes, dtype="<u8").view(np.uint8).reshape(a, -1)
+            bits = np.unpackbits(by, axis=1, count=n * m, bitorder="little").reshape(a, m, n)
+            bits.sum(axis=1, dtype=np.uint32), bits.sum(axis=2, dtype=np.uint32), bits.sum(axis=(1, 2), dtype=np.uint64)
+        cross.flagged_pairs(cs, 0, m, flagged)
+
+    def check_alone():
+        cs.check(0, m, flags=flags, now_ns=NOW, want_flagged=True)
+
+    def review_counts():
+        cs.review(0, m, flags=flags, now_ns=NOW, want_flagged=True)
+
+    def review_list():
+        cs.review(0, m, flags=flags, now_ns=NOW, want_flagged=True, pairs="flagged", pair_cap=cap)     # (one call: a cap the caller knows to be enough)
+    return [reduce_on_host, check_alone, review_counts, review_list]
+
+
+def ms(times):
+    return {"min": min(times) * 1e3, "median": float(np.median(times)) * 1e3, "max": max(times) * 1e3, "reps": len(times)}
+
+
 def launch_alone(table, db, reps, warmup):
     def body():
         table.launch(db, now_ns=NOW)
@@ -190,6 +223,8 @@ def main():
     ap.add_argument("--skip-host", action="store_true")
     ap.add_argument("--check-alone", default=None, metavar="NAME:N:M[:A][:rR]")
     ap.add_argument("--pairs", default=None, metavar="NAME:N:M:COUNT")
+    ap.add_argument("--review", default=None, metavar="NAME:N:M[:A]")
+    ap.add_argument("--profile-review", default=None, metavar="NAME:N:M[:A]")
     args = ap.parse_args()
     if args.reps < 10:
         ap.error("at least 10 timed repetitions")
@@ -201,6 +236,30 @@ def main():
         t = timed(table, args.reps, args.warmup, lambda: cs.check(0, m, now_ns=NOW) and None)
         print(json.dumps({"check_alone": args.check_alone, "kernel": cs.describe(), "a": len(a),
                           "direct_check_alone": stats(t, n * m * len(a)), "median_ms": float(np.median(t)) * 1e3}), flush=True)
+        cs.close()
+        table.close()
+        return
+    if args.review or args.profile_review:
+        name, n, m, na = parse(args.review or args.profile_review)
+        lt, table, fl, p, r, a = setup(name, n, m, na)
+        cs = direct_leg(lt, table, fl, p, r, a)()
+        flags = capi.F_WANT_DERIVED_ROLES if name == "c3" else 0
+        rv = cs.review(0, m, flags=flags, now_ns=NOW, want_flagged=True, pairs="flagged")
+        bodies = review_bodies(cs, n, m, len(a), flags, max(1024, 2 * rv.n_pairs))
+        if args.profile_review:
+            for _ in range(3):
+                bodies[2]()
+            print(json.dumps({"profile_review": args.profile_review, "kernel": cs.describe(flags), "reviews": 3,
+                              "plane_bytes_read_per_review": 2 * len(a) * ((n * m + 63) // 64) * 8}), flush=True)
+        else:
+            t = timed_alternating(table, args.reps, args.warmup, bodies)
+            line = {"review": args.review, "kernel": cs.describe(flags), "a": len(a), "decisions": n * m * len(a), "unit": "ms, wall clock",
+                    "allowed": int(rv.totals[0].sum()), "flagged": int(rv.totals[1].sum()), "flagged_pairs": rv.n_pairs,
+                    "a_check_numpy_counts_and_pairs": ms(t[0]), "b_check_alone": ms(t[1]), "c_review_counts": ms(t[2]), "d_review_counts_and_list": ms(t[3])}
+            line["c_median_over_b_median"] = line["c_review_counts"]["median"] / line["b_check_alone"]["median"]
+            line["a_median_over_c_median"] = line["a_check_numpy_counts_and_pairs"]["median"] / line["c_review_counts"]["median"]
+            line["a_median_over_d_median"] = line["a_check_numpy_counts_and_pairs"]["median"] / line["d_review_counts_and_list"]["median"]
+            print(json.dumps(line), flush=True)
         cs.close()
         table.close()
         return
