@@ -394,7 +394,7 @@ static int wf_finish(WireFlatten& f, cbh_device_batch** out) {
   if (st.heap_used >= (1u << 30)) return fail("cbh_wire_flatten: batch too large: nested attribute values exceed the heap's 30-bit offsets");   // (as cbi_flatten_pb)
   info->n_tuples = st.n_tuples; info->n_host = st.n_host; info->dict_slots = f.slots; info->heap_len = st.heap_used; info->fill_runs = f.runs;
   if (st.first_bad != CBH_NONE) { wf_bad_input(f, st.first_bad); return -1; }
-  if (st.n_host) { g_err = "cbh_wire_flatten: " + std::to_string(st.n_host) + " message(s) are the host flattener's (more than 64 actions, a resource kind to rewrite that no policy names, containers nested too deep)"; return 1; }
+  if (st.n_host) { g_err = "cbh_wire_flatten: " + std::to_string(st.n_host) + " message(s) are the host flattener's (more than 64 actions, a resource kind to rewrite that no policy names, containers nested too deep, a map that repeats a key or has more than 256 entries)"; return 1; }
   BatchDev& d = b->dev;
   batch_set_counts(b, n, st.n_tuples, st.n_roles, f.ncol, f.slots, st.heap_used);
   d.req_u32 = a.req_u32; d.roles = a.roles; d.tuple_req = nullptr; d.tuple_action = a.tuple_action; d.col_tag = a.col_tag; d.col_val = a.col_val;

@@ -564,7 +564,8 @@ __device__ inline int val_compare(const Ctx& c, Val a, Val b) {
   }
 }
 
-// map lookup by string key: entries are (key, value) pairs
+// map lookup by string key: entries are (key, value) pairs.  A map on the heap holds a key ONCE: the encoders see to it (a key the wire
+// repeats keeps its last entry, as protobuf maps decode - cbi_flatten.h map_tape; the device flattener leaves such a message to the host's)
 __device__ inline bool map_find(const Ctx& c, Val m, Val key, Val& out) {
   u32 n = cont_len(m.v), off = cont_off(m.v), sel = cont_sel(m.v);
   for (u32 i = 0; i < n; ++i) {

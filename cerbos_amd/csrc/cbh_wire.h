@@ -21,7 +21,8 @@
 // K + its slot: the decision kernels find its bytes through BatchDev.str_keys (cbh_vm.h str_view, cbh_resolve_globs_kernel).
 //
 // Scope of the device path: messages the host flattener would split (> 64 actions), rewrite (resource kinds of the pre-0.30
-// form, namer.go:213-218) or that nest containers deeper than CBH_WIRE_MAX_DEPTH are counted in WireStats.n_host and the
+// form, namer.go:213-218), that nest containers deeper than CBH_WIRE_MAX_DEPTH, that repeat a key of a map written to the heap
+// (the host flattener keeps the last entry of the key) or write a map of more than CBH_WIRE_MAX_MAP_ENTRIES entries there are counted in WireStats.n_host and the
 // caller takes the whole batch through libcerbos_ingest.so instead (product code, same result) - never a guess.
 // Same message grammar, same last-field-wins rules, same tags and values as cbh_ingest.cpp; tests/test_wire_device.py holds
 // the two against each other array by array.
@@ -34,6 +35,7 @@
 #define CBH_WIRE_MAX_ROLES 255u
 #define CBH_WIRE_MAX_STRLEN 0xFFFFu
 #define CBH_WIRE_MAX_VALUE_ENTRIES 0xFFFFFu   /* heap entries of one attribute value */
+#define CBH_WIRE_MAX_MAP_ENTRIES 256u   /* wire entries of ONE map written to the heap; a wider one: host flattener (the search for a repeated key is bounded by it) */
 #define CBH_WIRE_MAX_PROBES 256u
 #define CBH_WIRE_CUR_COLS 16u      /* columns whose first key is found by the one pass per attribute map (LDS: 8 B per column and lane) */
 
@@ -677,7 +679,8 @@ __global__ __launch_bounds__(CBH_BLOCK) void cbh_wire_scan_kernel(WireArgs a)
 }
 
 // ---- kernel 3: the batch ---------------------------------------------------------------------------------------------
-struct WFrame { WSpan rest; u32 slot; u32 is_map; };
+// (start: where the frame's entries begin, bit 31 = they are a map's; seen: a 32-bit filter of the key ids a map's frame has written)
+struct WFrame { WSpan rest; u32 slot; u32 start; u32 seen; };
 
 template <class MP>
 __device__ __forceinline__ u32 w_count_fields(MP m, WSpan s, u32 fnum, bool& bad) {
@@ -690,6 +693,11 @@ __device__ __forceinline__ u64 w_container(u32 off, u32 n) { return ((u64)CBH_HE
 // One container value - the entries of map field `fnum` of `body`, or the values (field 1) of a ListValue - and everything
 // nested in it, depth first.  WRITE = false: returns the heap entries it needs.  WRITE = true: writes them at [base, ..)
 // (the container's own entries first, each nested container's behind what was allocated before it) and returns the same.
+// A map that holds a key twice has one entry per key once decoded (the last stays), which changes its length and with it every
+// offset behind it: such a message is the host flattener's (CBH_WL_HOST from the write pass - it has the keys' ids, the counting
+// pass leaves the dictionary alone).  The filter keeps the search for an equal id among the entries written to the maps that need it;
+// the search is among at most CBH_WIRE_MAX_MAP_ENTRIES keys, since a wider map is the host flattener's too (both passes say so by its
+// count of entries, and the write pass then searches nothing): at most 64 loads per heap entry on average, whatever the request holds.
 struct WHeapDst { CBH_G u8* heap_tag; CBH_G u64* heap_val; u32 heap_cap; };
 template <bool WRITE, class MP>
 __device__ __attribute__((noinline)) u64 w_container_walk_fn(WTab t, WHeapDst a, MP m, u32 bias, WSpan body, u32 fnum, bool is_map, u32 base) {
@@ -699,10 +707,11 @@ __device__ __attribute__((noinline)) u64 w_container_walk_fn(WTab t, WHeapDst a,
   u32 depth = 0;
   const u32 n0 = w_count_fields(m, body, fnum, L.bad);
   u32 used = is_map ? 2u * n0 : n0;
-  st[0].rest = body; st[0].slot = base; st[0].is_map = is_map ? (0x80000000u | fnum) : fnum; depth = 1;
+  if (is_map && n0 > CBH_WIRE_MAX_MAP_ENTRIES) L.host = true;
+  st[0].rest = body; st[0].slot = base; st[0].start = base | (is_map ? 0x80000000u : 0u); st[0].seen = 0; depth = 1;
   while (depth && !L.bad) {
     WFrame& fr = st[depth - 1u];
-    const u32 want = fr.is_map & 0x7FFFFFFFu; const bool mp = (fr.is_map >> 31) != 0u;
+    const u32 want = depth == 1u ? fnum : 1u; const bool mp = (fr.start >> 31) != 0u;   // (below the root: Struct.fields = ListValue.values = 1)
     WField f; bool got = false;
     while (w_next(m, fr.rest, f, L.bad)) if (f.num == want && f.wt == 2u) { got = true; break; }
     if (!got) { --depth; continue; }
@@ -711,7 +720,12 @@ __device__ __attribute__((noinline)) u64 w_container_walk_fn(WTab t, WHeapDst a,
       WSpan k, v;
       if (!w_entry(m, f.s, k, v, L.bad)) break;
       const u32 kid = WRITE ? intern(k.p, k.e - k.p) : 0u;   // (the counting pass leaves the dictionary alone)
-      if (WRITE && fr.slot < a.heap_cap) { a.heap_tag[fr.slot] = (u8)CBH_T_STRING; a.heap_val[fr.slot] = kid; }
+      if (WRITE && fr.slot < a.heap_cap) {
+        const u32 bit = 1u << ((kid * 0x9E3779B1u) >> 27);
+        if (!L.host && (fr.seen & bit)) for (u32 s = fr.start & 0x7FFFFFFFu; s < fr.slot; s += 2u) if ((u32)a.heap_val[s] == kid) L.host = true;
+        fr.seen |= bit;
+        a.heap_tag[fr.slot] = (u8)CBH_T_STRING; a.heap_val[fr.slot] = kid;
+      }
       ++fr.slot;
       elem = v;
     }
@@ -727,12 +741,13 @@ __device__ __attribute__((noinline)) u64 w_container_walk_fn(WTab t, WHeapDst a,
         const u32 off2 = base + used;
         used += cm ? 2u * n2 : n2;
         tag = cm ? CBH_T_MAP : CBH_T_LIST; val = w_container(off2, n2);
+        if (cm && n2 > CBH_WIRE_MAX_MAP_ENTRIES) L.host = true;
         if (depth == CBH_WIRE_MAX_DEPTH) { L.host = true; tag = CBH_T_NULL; val = 0; }
         else if (n2) {
           const u32 slot = fr.slot;
           if (WRITE && slot < a.heap_cap) { a.heap_tag[slot] = (u8)tag; a.heap_val[slot] = val; }
           ++st[depth - 1u].slot;
-          st[depth].rest = v.s; st[depth].slot = off2; st[depth].is_map = cm ? (0x80000000u | 1u) : 1u;
+          st[depth].rest = v.s; st[depth].slot = off2; st[depth].start = off2 | (cm ? 0x80000000u : 0u); st[depth].seen = 0;
           ++depth;
           if (used > CBH_WIRE_MAX_VALUE_ENTRIES) { L.host = true; break; }
           continue;
@@ -979,7 +994,10 @@ __device__ __forceinline__ void w_fill_body(const WireArgs& a, MP m, const u32 b
               if (f.num != 2u || f.wt != 2u) continue;
               WSpan k, v;
               if (!w_entry(mc, f.s, k, v, L.bad)) break;
-              put(slot, CBH_T_STRING, w_intern(a, mc, bc, k.p, k.e - k.p, 0u, L));
+              const u32 kid = w_intern(a, mc, bc, k.p, k.e - k.p, 0u, L);
+              if (n_top > CBH_WIRE_MAX_MAP_ENTRIES) L.host = true;   // a name twice, or more names than the search is bounded to: the host flattener's
+              for (u32 s = off; !L.host && s < slot && s < a.heap_cap; s += 2u) if ((u32)a.heap_val[s] == kid) L.host = true;
+              put(slot, CBH_T_STRING, kid);
               put(slot + 1u, CBH_T_MAP, w_container(next, 1u));
               slot += 2u;
               put(next, CBH_T_STRING, sid_claims);

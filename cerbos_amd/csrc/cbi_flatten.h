@@ -111,6 +111,30 @@ struct Encoder {
     return TV{tag, container(off, tag == T_MAP ? items.size() / 2 : items.size())};
   }
 
+  // (key, value) pairs as a map with ONE entry per key: of a key the wire repeats, the last entry is the map's, as protobuf maps decode
+  // (the constant paths read it so: map_get, cbi_pb.h).  The earlier entries leave only what their values put on the heap before, which
+  // nothing points at.
+  TV map_tape(std::vector<TV>& ents) {
+    const size_t n = ents.size() / 2;
+    bool repeated = false;
+    if (n <= 16) {   // the common map: a few compares, no allocation
+      for (size_t i = 1; i < n && !repeated; ++i) for (size_t j = 0; j < i; ++j) if (ents[2 * j].val == ents[2 * i].val) { repeated = true; break; }
+    } else {
+      std::vector<u64> keys(n);
+      for (size_t i = 0; i < n; ++i) keys[i] = ents[2 * i].val;
+      std::sort(keys.begin(), keys.end());
+      repeated = std::adjacent_find(keys.begin(), keys.end()) != keys.end();
+    }
+    if (repeated) {
+      std::unordered_map<u64, size_t> last;
+      for (size_t i = 0; i < n; ++i) last[ents[2 * i].val] = i;
+      size_t w = 0;
+      for (size_t i = 0; i < n; ++i) if (last[ents[2 * i].val] == i) { ents[2 * w] = ents[2 * i]; ents[2 * w + 1] = ents[2 * i + 1]; ++w; }
+      ents.resize(2 * w);
+    }
+    return tape((u8)T_MAP, ents);
+  }
+
   // entries of a map<string, Value> field `fnum` of `msg`, children first, then the (key, value) pairs
   TV enc_map(Span msg, u32 fnum) {
     std::vector<TV> ents;
@@ -122,7 +146,7 @@ struct Encoder {
       ents.push_back(TV{(u8)T_STRING, in.sid(sv(en.key))});
       ents.push_back(enc(en.val));
     }
-    return tape((u8)T_MAP, ents);
+    return map_tape(ents);
   }
 
   TV enc(Span m) {
@@ -303,7 +327,7 @@ int flatten_slice(const cbi_table* t, const Source& src, uint32_t first, uint32_
               ents.push_back(TV{(u8)T_STRING, in.sid(sv(en.key))});
               ents.push_back(jwt_as_map(en.val));
             }
-            const TV tv = encd.tape((u8)T_MAP, ents);
+            const TV tv = encd.map_tape(ents);
             tag = tv.tag; val = tv.val; done = true;
           } else if (!map_get(m.aux, 2, col.keys[0], jwt, encd.bad)) { tag = nk == 1 ? (u8)T_ABSENT : (u8)T_ERR; done = true; }
           else if (nk == 1) { TV tv = jwt_as_map(jwt); tag = tv.tag; val = tv.val; done = true; }

@@ -567,7 +567,7 @@ def _index(v, i):
         if isinstance(i, bool) or not is_num(i):
             raise no_such_overload()
         if isinstance(i, float):
-            if i != int(i):
+            if i != i or i in (float("inf"), float("-inf")) or i != int(i):      # (int() of NaN / an infinity raises: cel-go's answer is this error)
                 raise CelError("unsupported index value")
             i = int(i)
         if i < 0 or i >= len(v):

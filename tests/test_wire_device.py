@@ -310,6 +310,26 @@ def test_nesting_and_width_boundaries():
     data, off = wire.pack_messages([wire.encode_check_input(i) for i in ok + [deep]])
     rc, wb2 = wu.sim_flatten(lt, data, off)
     assert rc == 0 and wb2.stats["n_host"] == 1 and wb2.stats["first_bad"] == 0xFFFFFFFF
+    # a key twice - only bytes can say it: k = 1, j = 2, k = 3.  The host flattener keeps ONE entry per key, the last; the device
+    # flattener leaves the message to it (tests/test_container_limits.py decides such maps on every road)
+    import struct
+    ld, val = wire._ld, lambda x: wire._varint(2 << 3 | 1) + struct.pack("<d", x)
+    r3 = base[3]["resource"]
+    m = b"".join(ld(1, ld(1, k) + ld(2, val(x))) for k, x in ((b"k", 1.0), (b"j", 2.0), (b"k", 3.0)))
+    res = wire.encode_resource(dict(r3, attr={})) + ld(4, ld(1, name.encode()) + ld(2, ld(5, m)))
+    twice = wire._string(1, "twice") + ld(2, res) + ld(3, wire.encode_principal(base[3]["principal"])) + b"".join(ld(4, a.encode()) for a in base[3]["actions"])
+    data, off = wire.pack_messages([wire.encode_check_input(i) for i in ok] + [twice])
+    it = IngestTable(lt.blob)
+    try:
+        hb = it.flatten_pb(data, off, sort=False)
+    finally:
+        it.close()
+    c = next(k for k, (root, keys) in enumerate(lt.columns) if root == "R" and tuple(keys) == (name,))
+    bits = lambda x: struct.unpack("<Q", struct.pack("<d", x))[0]   # noqa: E731
+    got = wu.decode_value(hb.col_tag[c, len(ok)], hb.col_val[c, len(ok)], hb.heap_tag, hb.heap_val, wu.Resolver(lt, host_batch=hb))
+    assert got == ("m", (("s", b"j"), (4, bits(2.0)), ("s", b"k"), (4, bits(3.0)))), got
+    rc, wb3 = wu.sim_flatten(lt, data, off)
+    assert rc == 0 and wb3.stats["n_host"] == 1 and wb3.stats["first_bad"] == 0xFFFFFFFF
 
 
 @pytest.mark.parametrize("name", ["C3", "C5", "fuzz1"])
