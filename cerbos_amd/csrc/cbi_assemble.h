@@ -170,7 +170,7 @@ int assemble_outputs(const cbi_table* t, const cbh_result* res, const uint8_t* b
 extern "C" {
 int cbi_assemble_pb_mt(const cbi_table* t, const cbi_batch* b, const cbh_result* res, const uint8_t* bytes, const uint64_t* offsets,
                        uint32_t n, const char* default_version, int n_threads, cbi_outputs** out) {
-  if (!t || !b || !res || !res->effect || !out || (n && (!bytes || !offsets))) return fail("cbi_assemble_pb: null argument");
+  if (!t || !b || !res || (!res->effect && b->view.n_tuples) || !out || (n && (!bytes || !offsets))) return fail("cbi_assemble_pb: null argument");   // (inputs without an action: no tuple, no array)
   std::string_view dver = default_version ? default_version : "default";
   TupleIndex ix;
   if (const char* e = ix.build(b, n, res->edr_mask, "batch does not belong to these inputs")) return fail(e);
@@ -185,7 +185,7 @@ int cbi_assemble_pb_mt(const cbi_table* t, const cbi_batch* b, const cbh_result*
 int cbi_assemble_wire_pb(const cbi_table* t, const cbh_result* res, const uint8_t* bytes, const uint64_t* offsets, uint32_t n,
                          uint32_t n_tuples, const uint32_t* in_span, const uint32_t* act_span, const uint32_t* act_off,
                          const char* default_version, int n_threads, cbi_outputs** out) {
-  if (!t || !res || !res->effect || !out || (n && (!bytes || !offsets || !in_span || !act_off)) || (n_tuples && !act_span)) return fail("cbi_assemble_wire_pb: null argument");
+  if (!t || !res || (!res->effect && n_tuples) || !out || (n && (!bytes || !offsets || !in_span || !act_off)) || (n_tuples && !act_span)) return fail("cbi_assemble_wire_pb: null argument");
   std::string_view dver = default_version ? default_version : "default";
   TupleIndex ix;   // from the device's own offsets: tuples in input order (no inv), derived roles per input already
   std::vector<u64>& first = ix.first;
@@ -210,7 +210,7 @@ int cbi_assemble_response_pb(const cbi_table* t, const cbi_batch* b, const cbh_r
 
 int cbi_assemble_response_traced_pb(const cbi_table* t, const cbi_batch* b, const cbh_result* res, const uint8_t* request, uint64_t request_len,
                                     const char* default_version, const cbi_outputs* traced, cbi_outputs** out) {
-  if (!t || !b || !res || !res->effect || !out || !request) return fail("cbi_assemble_response_pb: null argument");
+  if (!t || !b || !res || (!res->effect && b->view.n_tuples) || !out || !request) return fail("cbi_assemble_response_pb: null argument");
   const std::string_view dver = default_version ? default_version : "default";
   RequestParts rp;
   if (!split_request(request, request_len, rp)) return fail("malformed CheckResourcesRequest");

@@ -203,16 +203,20 @@ def to_batch(lt, wb, grouped=False):
     return b
 
 
-def sim_outputs(lt, res, n, cap=None, edr_is_grouped=False):
+def sim_outputs(lt, res, n, cap=None, edr_is_grouped=False, bias=0, with_offsets=False):
     """The device assembler (cbh_wire_out_* kernels, simulator) on the batch the LAST sim_flatten call built; ``res`` = a
-    capi.Result in input order.  -> ([serialized CheckOutput], flags uint8[n])"""
+    capi.Result in input order.  -> ([serialized CheckOutput], flags uint8[n]); ``bias``: the output buffer starts that many bytes
+    behind a 16-byte boundary (WireOutArgs.out_bias takes every value 0..15); ``with_offsets``: the kernels' offsets uint64[n + 1] as a
+    third value."""
     lib = hostsim_api.lib()
     lib.hostsim_wire_outputs.argtypes = [C.c_void_p, C.c_size_t] + [C.c_void_p] * 6 + [C.c_size_t, C.c_void_p, C.c_void_p, C.c_int]
     lib.hostsim_wire_outputs.restype = C.c_longlong
     buf = C.create_string_buffer(lt.blob, len(lt.blob))
     cap = 256 if cap is None else cap
     while True:
-        out = np.zeros(cap + 8, np.uint8)
+        room = np.zeros(cap + 8 + 32, np.uint8)
+        start = (-room.ctypes.data) % 16 + (bias & 15)
+        out = room[start:start + cap + 8]
         off = np.zeros(n + 1, np.uint64)
         flags = np.zeros(n + 1, np.uint8)
         need = lib.hostsim_wire_outputs(C.cast(buf, C.c_void_p), len(lt.blob), res.effect.ctypes.data, res.policy.ctypes.data, res.scope.ctypes.data,
@@ -222,5 +226,7 @@ def sim_outputs(lt, res, n, cap=None, edr_is_grouped=False):
         if need <= cap:
             raw = out.tobytes()
             assert int(off[n]) == need
-            return [raw[int(off[i]):int(off[i + 1])] for i in range(n)], flags[:n]
+            assert not room[:start].any() and not room[start + int(need):].any(), "bytes written outside the outputs' range"
+            outs = [raw[int(off[i]):int(off[i + 1])] for i in range(n)]
+            return (outs, flags[:n], off) if with_offsets else (outs, flags[:n])
         cap = int(need)
