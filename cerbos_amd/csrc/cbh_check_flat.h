@@ -537,6 +537,7 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c, con
   u32 cls_a0 = 0, cls_r0 = 0;
   bool spec = false; u32 spec_ix = 0;
   u32 x_prow = 0, x_rrow = 0;   // CROSS: the lane's two rows of the halves
+  u32 c_first = CBH_NONE;       // COMPACT: the chain's first scope, from the record (cbh_vm.h cbh_creq_first)
   u32 x_done = 0;               // CROSS, role group >= 1: bit k = an earlier group's role allowed action k
   u32 act_total = 0;            // AGROUP: the request's action count (act_cnt is the group's)
   if constexpr (CROSS) {
@@ -546,7 +547,7 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c, con
     x_rrow = x.n + (x.r_order ? x.r_order[x.r_begin + jp] : x.r_begin + jp);
     const u32x4u prec = load_u32x4(b.creq + 4u * (size_t)x_prow), rrec = load_u32x4(b.creq + 4u * (size_t)x_rrow);
     pid = prec.x; kind = rrec.y & 0xFFFFu; r_ver = rrec.y >> 16;
-    r_scope = (rrec.z & 0xFFFFu) | (rrec.w & CBH_SCOPE_EXACT);
+    r_scope = 0; c_first = cbh_creq_first(rrec.z, rrec.w, (flags & CBH_F_LENIENT_SCOPE_SEARCH) != 0);   // (the resource's record: resolved when the halves were uploaded)
     role_cnt = valid ? (prec.z >> 16) & 7u : 0u; act_cnt = valid ? (x.act_word >> 20) & 7u : 0u;   // both <= 4
 #pragma unroll
     for (u32 k = 0; k < 4; ++k) ac[k] = valid ? (x.act_word >> (5u * k)) & 31u : 31u;
@@ -573,13 +574,17 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c, con
     }
   } else if constexpr (COMPACT) {
     // ---- the compact form (cbh_vm.h BatchDev.creq): ONE 16-byte load brings everything the walk takes from the request words, the
-    // role ids and the action ids - the classes were looked up when the batch was uploaded.  First trip: the record; second:
-    // the columns' and the tags' copies (cc_fill_compact) and the chain's first scope.  No class table is read, none is staged in LDS, and the
-    // prologue has no barrier of its own.
-    const u32x4u rec = load_u32x4(b.creq + 4u * (size_t)req);
+    // role ids and the action ids - the classes and the chain's first scope were looked up when the batch was uploaded.  ONE trip
+    // to memory: the record (first: the largest item, and a build with the copies in front of it was slower) and the columns' and
+    // the tags' copies (cc_fill_compact: right behind it, while nothing else is live, back to back) share one wait.  No class table and no scope array is read, none is staged in LDS, and the prologue has no barrier
+    // of its own.  (No LDS store of this prologue lies in front of the copies but cc_fill_compact's own zero fills: the compact
+    // instantiations have no trail.)
+    static_assert(!EP, "the compact instantiations keep no trail: its LDS stores would have to go in front of the copies");
+    const u32x4u rec = load_u32x4(b.creq + 4u * (size_t)req);   // (first: the largest item of the trip, in flight while the copies are issued)
+    cc_fill_compact(c, b, NR, w0, wd);
     pid = rec.x; kind = rec.y & 0xFFFFu; r_ver = rec.y >> 16;
     const u32 w2 = valid ? rec.z : ((rec.z & 0xFFFFu) | 0xFFC00000u), w3 = valid ? rec.w : (rec.w | 0x3FFFFFFFu);   // (a lane beyond the batch's end: no action, no role)
-    r_scope = (w2 & 0xFFFFu) | (w3 & CBH_SCOPE_EXACT);
+    r_scope = 0; c_first = cbh_creq_first(w2, w3, (flags & CBH_F_LENIENT_SCOPE_SEARCH) != 0);   // (a lane beyond the end keeps the shadowed request's, as before)
     role_cnt = (w2 >> 16) & 7u; act_cnt = (w2 >> 19) & 7u;   // both <= 4
 #pragma unroll
     for (u32 k = 0; k < 4; ++k) ac[k] = (w3 >> (5u * k)) & 31u;
@@ -661,11 +666,13 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c, con
   CBH_L u32* ep_lds = (CBH_L u32*)(cls_lds + (cls_in_lds ? ((2u * t.K + 15u) & ~15u) : 0u) + (MODE == 2 ? CBH_FLAT_WAVES * CBH_SEG_LDS_BYTES : 0u)) + wave * max_depth * 2u * CBH_BLOCK;
   const bool want_ep = EP && (flags & CBH_F_WANT_EFFECTIVE_POLICIES) != 0 && o.eff_pol != nullptr;
   if (EP) { for (u32 d = 0; d < 2u * max_depth; ++d) ep_lds[d * CBH_BLOCK + c.tid] = 0; }
-  if constexpr (CROSS) cc_fill_cross(c, b, NR, x_prow, x_rrow, x.side); else if constexpr (COMPACT) cc_fill_compact(c, b, NR, w0, wd); else cc_fill(c, b, NR, w0, wd, cct);   // (behind every LDS store of this prologue)
+  if constexpr (CROSS) cc_fill_cross(c, b, NR, x_prow, x_rrow, x.side); else if constexpr (!COMPACT) cc_fill(c, b, NR, w0, wd, cct);   // (behind every LDS store of this prologue; COMPACT: issued above, with the record)
   // ... and the chain's first scope (ruletable.go:848-882; per lane, reads the scope tables): its load goes out with the second trip
   const bool lenient = (flags & CBH_F_LENIENT_SCOPE_SEARCH) != 0;
   // (AGROUP, a later group: a lane whose request has no action in it stands at no scope - it takes no part in the walk or in the second climb)
-  const u32 first_own = chain_first(t, r_scope, FLAG_RES, lenient);
+  // (COMPACT: it came with the record - no trip to the scope arrays)
+  u32 first_own;
+  if constexpr (COMPACT) first_own = c_first; else first_own = chain_first(t, r_scope, FLAG_RES, lenient);
   const u32 first = (AGROUP && ag.group != 0u && act_cnt == 0u) ? CBH_NONE : first_own;
   if constexpr (COMPACT) {
   } else if (cls_in_lds) {
@@ -1098,7 +1105,9 @@ __device__ __forceinline__ void flat_body(const KernelArgs& ka_regs, Ctx& c, con
         dp0 |= (mydepth & 1u) ? newly : 0u; dp1 |= (mydepth & 2u) ? newly : 0u; dp2 |= (mydepth & 4u) ? newly : 0u; dp3 |= (mydepth & 8u) ? newly : 0u;
       }
     }
-    const u32 up = uchain_next(t, uload(&t.scope_parent[g_si]), FLAG_RES);   // check.go:231
+    // (COMPACT, a table of one scope: `cur` becomes CBH_NONE whatever the parent is - its two loads and their wait are not issued.
+    // The wide-input instantiations keep the code they were measured with)
+    const u32 up = (COMPACT && max_depth <= 1u) ? CBH_NONE : uchain_next(t, uload(&t.scope_parent[g_si]), FLAG_RES);   // check.go:231
     if (ing) { cur = (mydepth + 1u < max_depth) ? up : CBH_NONE; ++mydepth; }
   }
 
@@ -1477,6 +1486,7 @@ struct CompactArgs {
   const CBH_G u8* col_tag; CBH_G u32* ctag;   // ctag: [(n_cached + 3) / 4][n_requests], four columns' tag bytes to a dword
   CBH_G u32* creq; CBH_G u32* cval; CBH_G u32* info;   // info[0]: bit k = column k has a high word, CBH_CI_MISFIT, CBH_CI_ACT4 INVERTED (some request is not aligned)
   u32 n_requests, n_cached, K, narrow;
+  const CBH_G u32* scope_parent; const CBH_G u32* scope_flags; u32 n_scopes;   // the table's: the pack resolves the chain's first scope (cbh_vm.h cbh_creq_first)
 };
 __global__ __launch_bounds__(256) void cbh_compact_scan_kernel(CompactArgs a) {
   const u32 r = blockIdx.x * 256u + threadIdx.x;
@@ -1513,10 +1523,20 @@ __global__ __launch_bounds__(256) void cbh_compact_pack_kernel(CompactArgs a) {
     ac[k] = (k < act_cnt && aid < a.K && ca < 31u) ? ca : 31u;
     rc[k] = (k < role_cnt && rid < a.K && cr < 31u) ? cr : 31u;
   }
+  // the chain's first scope by chain_first's own rule (cbh_kernels.h; FLAG_RES), under both searches: a resident batch is bound to
+  // its table, so what the flat kernels' prologue looked up per launch - a dependent trip to the scope arrays - is looked up here, once
+  const u32 si = r_scope & ~CBH_SCOPE_EXACT;
+  u32 first = CBH_NONE;
+  bool strict = false;
+  if (si < a.n_scopes) {
+    strict = (r_scope & CBH_SCOPE_EXACT) != 0 && (a.scope_flags[si] & FLAG_RES) != 0;
+    first = si;
+    while (first != CBH_NONE && !(a.scope_flags[first] & FLAG_RES)) first = a.scope_parent[first];
+  }
   CBH_G u32* rec = a.creq + 4u * (size_t)r;
   rec[0] = pid; rec[1] = cbh_creq_w1(kind, r_ver);
-  rec[2] = cbh_creq_w2(r_scope, role_cnt, act_cnt, rc[2], rc[3]);
-  rec[3] = cbh_creq_w3(r_scope, ac[0], ac[1], ac[2], ac[3], rc[0], rc[1]);
+  rec[2] = cbh_creq_w2(first, role_cnt, act_cnt, rc[2], rc[3]);
+  rec[3] = cbh_creq_w3(first, strict, ac[0], ac[1], ac[2], ac[3], rc[0], rc[1]);
   u32 plane = 0;
   for (u32 k = 0; k < a.n_cached; ++k)
     if ((a.narrow >> k) & 1u) { a.cval[plane * NR + r] = (u32)a.col_val[k * NR + r]; ++plane; }

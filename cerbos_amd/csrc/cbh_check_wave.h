@@ -494,28 +494,77 @@ __device__ __forceinline__ void cc_fill(const Ctx& c, const BatchDev& b, u32 NR,
 // four columns, of the lane's dword of the batch's `ctag` plane, straight into the cache's packed tag plane - nothing through a
 // register, no byte position per lane.  A compact launch always has the packed form of the cache (the host sets CBH_FI_PACKED_TAGS
 // and sizes the LDS for it: cbh_host_resident.h launch_plan), so every reader of the cache sees what cc_fill would have left there.
+//
+// All copies go out back to back, and each costs a handful of scalar instructions.  Written as loops over c.n_cached the three steps
+// stayed loops, and the tag loop and the column loop each re-read their kernel arguments and waited for them on every iteration:
+// some ten scalar-memory waits between the first copy and the last on a table of six columns.  So:
+//   - what the copies need is read ONCE, in front of the first of them, and MOVED into scalar registers of its own (cc_hold: a
+//     real move behind `asm volatile` - the compiler may not read the argument again, and the sixteen-dword argument load the
+//     values came with is dead behind the moves; held in place, its registers were spilled and restored as a whole at every column);
+//   - each step is unrolled over CBH_CACHE_COLS behind wave-uniform forward guards - no scalar-memory wait and no backward branch
+//     between the first copy and the last (tools/audit_prologue_waits.py --max-first-trip-scalar-waits);
+//   - the wave's first request and its slice of the cache go through readfirstlane HERE (they are uniform, but formed from the
+//     wave's number in a vector register): a copy's global address is a scalar base plus the lane's 32-bit offset, its LDS
+//     address a scalar sum - no 64-bit vector arithmetic and no read-back per copy.
+// The caller issues this before anything else of its prologue is live, every lane active.
+template <typename T> __device__ __forceinline__ T cc_hold(T x) {
+#ifndef CBH_HOSTSIM
+  T y;
+  if constexpr (sizeof(T) == 8) asm volatile("s_mov_b64 %0, %1" : "=s"(y) : "s"(x)); else asm volatile("s_mov_b32 %0, %1" : "=s"(y) : "s"(x));
+  return y;
+#else
+  return x;
+#endif
+}
+__device__ __forceinline__ CBH_L u32* cc_uniform_lds(CBH_L u32* p) {
+#ifndef CBH_HOSTSIM
+  return (CBH_L u32*)(size_t)uniform((u32)(size_t)p);   // (an LDS address is 32 bits)
+#else
+  return p;
+#endif
+}
+// the copies of column K and of the columns behind it; `plane` = the narrow planes in front of column K (uniform); `d` = the lane's
+// distance from the wave's first request r0.  Spelled as a recursion over K, not as a loop with `#pragma unroll`: the compiler folded
+// that loop's exit into a run-time trip count and unrolled it by two - a loop again, with backward branches between the copies.
+template <u32 K>
+__device__ __forceinline__ void cc_cols_compact(CBH_L u32* cc, CBH_L u32* hi, const CBH_G u32* cval, const CBH_G u64* col_val, u32 n, u32 narrow,
+                                                u32 nr, u32 r0, u32 d, u32 plane, u32 tid) {
+  if constexpr (K < CBH_CACHE_COLS) {
+    if (K >= n) return;
+    // the low words: ONE copy whichever the column's form - its plane and its lane stride are chosen on the scalar unit, not by a branch
+    const bool nb = ((narrow >> K) & 1u) != 0;
+    const u32 sh = nb ? 2u : 3u;
+    const CBH_G char* plane0 = nb ? (const CBH_G char*)(cval + (size_t)plane * nr) : (const CBH_G char*)(col_val + (size_t)K * nr);
+    const CBH_G char* vb = plane0 + ((size_t)r0 << sh);   // uniform
+    const u32 off = d << sh;
+    lds_dma_dword(vb + off, cc + K * CBH_BLOCK, tid);
+    if (!nb) lds_dma_dword(vb + 4 + off, hi + K * CBH_BLOCK, tid);   // (a narrow column's high plane was zero-filled)
+    cc_cols_compact<K + 1>(cc, hi, cval, col_val, n, narrow, nr, r0, d, plane + (nb ? 1u : 0u), tid);
+  }
+}
 __device__ __forceinline__ void cc_fill_compact(const Ctx& c, const BatchDev& b, u32 NR, u32 req0, u32 d) {
-  const u32 narrow = b.compact_info & CBH_CI_NARROW_MASK;   // uniform
-  CBH_L u32* tags = c.cc + 2u * c.n_cached * CBH_BLOCK;
-  for (u32 k = 0; k < c.n_cached; ++k) if ((narrow >> k) & 1u) c.cc[(c.n_cached + k) * CBH_BLOCK + c.tid] = 0u;
-  const u32 d4 = d * 4u, d8 = d * 8u;
-  for (u32 g = 0; 4u * g < c.n_cached; ++g) {
-    const CBH_G char* tb = (const CBH_G char*)(b.ctag + ((size_t)g * NR + req0));   // uniform
+  const CBH_G u32* const cval = cc_hold(b.cval); const CBH_G u32* const ctag = cc_hold(b.ctag); const CBH_G u64* const col_val = cc_hold(b.col_val);
+  const u32 n = cc_hold(c.n_cached < CBH_CACHE_COLS ? c.n_cached : CBH_CACHE_COLS);
+  const u32 narrow = cc_hold(b.compact_info & CBH_CI_NARROW_MASK);   // uniform
+  const u32 nr = cc_hold(NR);
+  const u32 r0 = uniform(req0);
+  CBH_L u32* const cc = cc_uniform_lds(c.cc);
+  CBH_L u32* const hi = cc + n * CBH_BLOCK;
+  CBH_L u32* const tags = cc + 2u * n * CBH_BLOCK;
+  const u32 zero = narrow & ((1u << n) - 1u);   // the narrow columns that exist
+#pragma unroll
+  for (u32 k = 0; k < CBH_CACHE_COLS; ++k) {
+    if ((zero >> k) == 0u) break;
+    if ((zero >> k) & 1u) hi[k * CBH_BLOCK + c.tid] = 0u;
+  }
+  const u32 d4 = d * 4u;
+#pragma unroll
+  for (u32 g = 0; g < CBH_CACHE_COLS / 4; ++g) {
+    if (4u * g >= n) break;
+    const CBH_G char* tb = (const CBH_G char*)(ctag + ((size_t)g * nr + r0));   // uniform
     lds_dma_dword(tb + d4, tags + g * CBH_BLOCK, c.tid);
   }
-  u32 plane = 0;   // narrow planes in front of column k (uniform)
-  for (u32 k = 0; k < c.n_cached; ++k) {
-    if ((narrow >> k) & 1u) {
-      const CBH_G char* vb = (const CBH_G char*)(b.cval + ((size_t)plane * NR + req0));
-      lds_dma_dword(vb + d4, c.cc + k * CBH_BLOCK, c.tid);
-      ++plane;
-    } else {
-      const CBH_G char* vb = (const CBH_G char*)(b.col_val + ((size_t)k * NR + req0));
-      const CBH_G char* vb4 = vb + 4;
-      lds_dma_dword(vb + d8, c.cc + k * CBH_BLOCK, c.tid);
-      lds_dma_dword(vb4 + d8, c.cc + (c.n_cached + k) * CBH_BLOCK, c.tid);
-    }
-  }
+  cc_cols_compact<0>(cc, hi, cval, col_val, n, narrow, nr, r0, d, 0u, c.tid);
 }
 
 // What the direct cross kernels (cbh_check_flat.h flat_body CROSS; cerbos_hip.h cbh_cross_check) take beside KernelArgs, as a

@@ -120,6 +120,7 @@ static int batch_compact(cbh_device_batch* b, hipStream_t s) {
   CompactArgs ca{};
   ca.req_u32 = d.req_u32; ca.roles = d.roles; ca.tuple_action = d.tuple_action; ca.col_val = d.col_val; ca.col_tag = d.col_tag;
   ca.action_class = dev.action_class; ca.role_class = dev.role_class; ca.K = dev.K;
+  ca.scope_parent = dev.scope_parent; ca.scope_flags = dev.scope_flags; ca.n_scopes = dev.n_scopes;
   ca.n_requests = d.n_requests; ca.n_cached = d.n_columns < CBH_CACHE_COLS ? d.n_columns : CBH_CACHE_COLS;
   if (dalloc(b, ca.info, 1) != 0) return -1;
   const dim3 grid((d.n_requests + 255u) / 256u);

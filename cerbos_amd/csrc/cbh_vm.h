@@ -106,8 +106,14 @@ struct BatchDev {
 // A request record is four words, record-major - everything flat_body takes from req_u32, roles and tuple_action:
 //   word 0  principal id
 //   word 1  kind (16) | resource version << 16                      (string ids; a batch with an id of 2^16 or more keeps the wide form)
-//   word 2  resource scope index (16) | role count << 16 (3) | action count << 19 (3) | role class 2 << 22 (5) | role class 3 << 27 (5)
-//   word 3  action classes 0..3 (5 each) | role class 0 << 20 | role class 1 << 25 | bit 30 spare | CBH_SCOPE_EXACT (bit 31)
+//   word 2  first scope of the chain (16) | role count << 16 (3) | action count << 19 (3) | role class 2 << 22 (5) | role class 3 << 27 (5)
+//   word 3  action classes 0..3 (5 each) | role class 0 << 20 | role class 1 << 25 | CBH_CREQ_FIRST_LENIENT (bit 30) | CBH_CREQ_FIRST_STRICT (bit 31)
+// The scope field is not the request's scope word but what the chain's first scope comes to (cbh_kernels.h chain_first, FLAG_RES),
+// resolved once per request when the batch is uploaded - the table's scope arrays and the request's scope word are the same at every
+// launch of a resident batch: the field holds the scope the lenient search stands at first (the request's scope, or its nearest
+// ancestor with a resource policy), bit 30 says that there is one, bit 31 that the strict search succeeds (the scope is the
+// table's own, exactly, and has a resource policy) - the field is then that scope.  cbh_creq_first decodes it for either search, so
+// one batch serves launches that alternate CBH_F_LENIENT_SCOPE_SEARCH, and a compact launch never reads the scope arrays for it.
 // The classes are what the wide prologue computes from the ids and the table's two class tables, clamps included (31 = a string no
 // rule names, or an action / role the request does not have): a resident batch is bound to one immutable table image.
 // A cached column whose values' high words are zero in every request of the batch has a plane of its low words in `cval`; the
@@ -118,11 +124,19 @@ struct BatchDev {
 #define CBH_CI_ACT4 0x10000u
 #define CBH_CI_MISFIT 0x20000u   /* (the scan's verdict only, never in BatchDev: a field does not fit the record) */
 __host__ __device__ __forceinline__ u32 cbh_creq_w1(u32 kind, u32 ver) { return kind | (ver << 16); }
-__host__ __device__ __forceinline__ u32 cbh_creq_w2(u32 r_scope, u32 role_cnt, u32 act_cnt, u32 rc2, u32 rc3) {
-  return (r_scope & 0xFFFFu) | (role_cnt << 16) | (act_cnt << 19) | (rc2 << 22) | (rc3 << 27);
+#define CBH_CREQ_FIRST_LENIENT 0x40000000u   /* word 3: the lenient scope search finds a first scope - the field of word 2 */
+#define CBH_CREQ_FIRST_STRICT 0x80000000u    /* word 3: the strict search does - the same field */
+// `first`: the chain's first scope under the lenient search, or CBH_NONE; `strict`: the strict search succeeds (first is then the request's own scope)
+__host__ __device__ __forceinline__ u32 cbh_creq_w2(u32 first, u32 role_cnt, u32 act_cnt, u32 rc2, u32 rc3) {
+  return (first != 0xFFFFFFFFu ? first & 0xFFFFu : 0u) | (role_cnt << 16) | (act_cnt << 19) | (rc2 << 22) | (rc3 << 27);
 }
-__host__ __device__ __forceinline__ u32 cbh_creq_w3(u32 r_scope, u32 ac0, u32 ac1, u32 ac2, u32 ac3, u32 rc0, u32 rc1) {
-  return ac0 | (ac1 << 5) | (ac2 << 10) | (ac3 << 15) | (rc0 << 20) | (rc1 << 25) | (r_scope & 0x80000000u);
+__host__ __device__ __forceinline__ u32 cbh_creq_w3(u32 first, bool strict, u32 ac0, u32 ac1, u32 ac2, u32 ac3, u32 rc0, u32 rc1) {
+  return ac0 | (ac1 << 5) | (ac2 << 10) | (ac3 << 15) | (rc0 << 20) | (rc1 << 25) | (first != 0xFFFFFFFFu ? CBH_CREQ_FIRST_LENIENT : 0u) |
+         (strict ? CBH_CREQ_FIRST_STRICT : 0u);
+}
+// the chain's first scope of a record under the launch's scope search, or CBH_NONE (0xFFFFFFFF)
+__host__ __device__ __forceinline__ u32 cbh_creq_first(u32 w2, u32 w3, bool lenient) {
+  return (w3 & (lenient ? CBH_CREQ_FIRST_LENIENT : CBH_CREQ_FIRST_STRICT)) ? (w2 & 0xFFFFu) : 0xFFFFFFFFu;
 }
 
 struct OutDev {

@@ -16,7 +16,13 @@ tables, the per-lane loop that climbs to a scope with a policy) all show up; wha
 
 Exit status 1 if a listed kernel's prologue has more than --max-bulk-trips (default 3) BULK trips - trips that carry asynchronous copies
 or at least eight loads of a dword or more: the request words with everything else that depends on nothing; the role ids with the fallback action ids
-(the static order puts a wait between them and the copies); the columns' copies.  Round 5's library has five."""
+(the static order puts a wait between them and the copies); the columns' copies.  Round 5's library has five.
+
+Two stricter checks, off by default (tests/test_compact_prologue_trips.py turns them on for the compact instantiations):
+    --max-trips N                       exit status 1 if more than N trips carry ANY load before the barrier or the scan's limit
+    --max-first-trip-scalar-waits K     exit status 1 if more than K `s_waitcnt lgkmcnt(0)`, or any backward branch, lie between the
+                                        first vector load and the first `vmcnt(0)`: what makes the LAST load of the first trip leave
+                                        later than its first - kernel arguments read again and waited for, a loop around the copies"""
 import argparse
 import os
 import re
@@ -32,6 +38,9 @@ ap.add_argument("kernels", nargs="*", default=["cbh_check_flat_kernel10", "cbh_c
                                                "cbh_check_flat_kernel_masks_c10", "cbh_check_flat_kernel_dr_x10", "cbh_walk2_kernel10"])
 ap.add_argument("--lib", default=os.path.join(ROOT, "cerbos_amd", "libcerbos_hip.so"))
 ap.add_argument("--max-bulk-trips", type=int, default=3)
+ap.add_argument("--max-trips", type=int, default=None, help="fail if a kernel has more trips that carry ANY load before the barrier or the scan limit")
+ap.add_argument("--max-first-trip-scalar-waits", type=int, default=None,
+                help="fail if more `s_waitcnt lgkmcnt(0)`, or any backward branch, lie between the first vector load and the first vmcnt(0)")
 args = ap.parse_args()
 
 with tempfile.TemporaryDirectory() as tmp:
@@ -85,4 +94,27 @@ for want in args.kernels:
         if len(bulk) > args.max_bulk_trips:
             print("    %d BULK trips (more than %d): read the disassembly around the extra waits" % (len(bulk), args.max_bulk_trips))
             bad = 1
+        if args.max_trips is not None and len(carrying) > args.max_trips:
+            print("    %d trips that carry loads (more than %d)" % (len(carrying), args.max_trips))
+            bad = 1
+        if args.max_first_trip_scalar_waits is not None:
+            # what delays the LAST load of the first trip behind its first: a wait for scalar memory (the kernel's arguments read
+            # again), a loop (a backward branch: its 16-bit word offset is negative)
+            swaits = back = 0
+            inside = False
+            for x in body[:end]:
+                f = x.split()
+                if f[0].startswith(("global_load", "buffer_load", "flat_load")):
+                    inside = True
+                elif f[0] == "s_waitcnt" and "vmcnt(0)" in x:
+                    if inside:
+                        break
+                elif inside and f[0] == "s_waitcnt" and "lgkmcnt(0)" in x:
+                    swaits += 1
+                elif inside and f[0].startswith(("s_branch", "s_cbranch")) and len(f) > 1 and f[1].isdigit() and int(f[1]) >= 0x8000:
+                    back += 1
+            print("    first trip: %d scalar-memory waits, %d backward branches between its first load and its wait" % (swaits, back))
+            if swaits > args.max_first_trip_scalar_waits or back:
+                print("    more than %d scalar-memory waits, or a loop, inside the first trip" % args.max_first_trip_scalar_waits)
+                bad = 1
 sys.exit(bad)
