@@ -51,7 +51,7 @@ B_RPROLES, B_FAMILY = 8, 9
 B_RESSEG = 10                         # (ver sid, kind sid, scope idx) -> v0 first segment block (16-dword units of CBH_SEC_SEGS), v1 segments, v2 dr_begin, v3 dr_count
 SEC_SEGS, SEC_LEAFPOOL = 43, 44
 M_SEGS = 23                           # CBH_M_SEGS: M_SEGS_PRESENT | M_SEGS_POOLED | leaves in CBH_SEC_LEAFPOOL
-M_SEGS_PRESENT, M_SEGS_POOLED, M_SEGS_ITEMS_POOLED = 1 << 31, 1 << 30, 1 << 29
+M_SEGS_PRESENT, M_SEGS_POOLED = 1 << 31, 1 << 30
 SEG_RECORDS = 64                      # records (and distinct conditions, and distinct leaves) per segment: one bit each of a 64-bit mask
 SEG_TAIL_PAD = 20                     # 16-dword units behind the last block: every lane loads an item descriptor slot, whatever n_items
 SEG_COMPLEX = 16                      # items of a segment the lanes cannot decide by themselves (deeper trees, more than four leaves, programs)
@@ -1272,8 +1272,7 @@ def _segments(res_entries, row_cols, leaf2_cols, pb):
     and the first DENY of a walk is a count-trailing-zeros - no record is visited.
 
     A table whose conditions are built from at most 64 distinct fused leaves is POOLED: the leaves are numbered table-wide and
-    live once in CBH_SEC_LEAFPOOL, and what a wave evaluated for one bucket serves the next; with at most 64 distinct
-    conditions the items are numbered table-wide too (ITEMS_POOLED).
+    live once in CBH_SEC_LEAFPOOL, and what a wave evaluated for one bucket serves the next.
     Returns (words of the section, leaf pool, directory entries, stats)."""
     NONE_ = 0xFFFFFFFF
 

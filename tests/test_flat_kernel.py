@@ -251,17 +251,27 @@ def test_segments_of_a_table_that_is_not_pooled():
     for i in inputs:
         i["resource"]["scope"] = ""
     batch = Flattener(lt).flatten(inputs)
-    res = hostsim_api.check(lt, batch, NOW, capi.F_WANT_DERIVED_ROLES)
+    from test_hostsim_golden import HostSimEvaluator
+    ev = HostSimEvaluator(lt, Conf())
+    res = ev.table.check(batch, now_ns=NOW, flags=capi.F_WANT_DERIVED_ROLES)
     assert hostsim_api.lib().hostsim_last_masks() == 1
+    assert not (res.status == capi.ST_UNSUPPORTED).any()
+    outs, bad = ev.assemble(inputs, batch, res, "default", allow_unsupported=True)
+    assert not bad
     orc = RuleTableOracle(rt)
-    t = 0
-    for inp in inputs:
+    t = n_allow = n_err = 0
+    for inp, have in zip(inputs, outs):
         want = orc.check(inp, EvalParams(now_ns=NOW))
+        assert norm_actions(have) == norm_actions(want), (inp, have, want)   # effect, policy key and scope of every action
+        assert sorted(have["effectiveDerivedRoles"]) == sorted(want.get("effectiveDerivedRoles") or []), inp
         for a in inp["actions"]:
             assert (res.effect[t] == capi.EFFECT_ALLOW) == (want["actions"][a]["effect"] == "EFFECT_ALLOW"), (inp, a)
+            n_allow += want["actions"][a]["effect"] == "EFFECT_ALLOW"
             t += 1
         na = len(inp["actions"])
         assert bool((res.status[t - na:t] == capi.ST_CEL_ERROR).any()) == bool(want.get("evaluationErrors"))
+        n_err += bool(want.get("evaluationErrors"))
+    assert n_allow > 20 and n_err > 5, (n_allow, n_err)
 
 
 def test_error_cases_do_occur():

@@ -583,7 +583,7 @@ def run_road(capi, road, only=None):
 CHILD = """
 import sys
 sys.path.insert(0, %(tests)r)
-import test_scope_limits as ts
+import %(module)s as ts
 if %(sim)r:
     from sim_engine import sim_engine
     with sim_engine() as capi:
@@ -591,20 +591,21 @@ if %(sim)r:
 else:
     from cerbos_amd import capi
     ts.run_road(capi, %(road)r)
-print("scope limits: ok")
+print("%(module)s: ok")
 """
 _ABNORMAL = []   # the first child that a signal or its time limit ended: no child is started after it
 
 
-def check_in_child(sim, road, lib=None, limit=600):
+def check_in_child(sim, road, lib=None, limit=600, module="test_scope_limits", library=None):
     """One fresh process per forced variant (the library reads its switches once), one after another, each under its own time
-    limit.  After a child that ended abnormally none is started."""
+    limit.  After a child that ended abnormally none is started.  `module`, `library`: another test file's road table (its
+    run_road(capi, road) is what the child calls)."""
     assert not _ABNORMAL, "not started: an earlier child ended abnormally (%s)" % _ABNORMAL[0]
-    env = dict(os.environ, **LIBRARY[road][0])
+    env = dict(os.environ, **(LIBRARY if library is None else library)[road][0])
     if lib:
         env["CBH_TEST_SIM_LIB"] = lib
     try:
-        r = subprocess.run([sys.executable, "-c", CHILD % {"tests": os.path.join(ROOT, "tests"), "sim": sim, "road": road}],
+        r = subprocess.run([sys.executable, "-c", CHILD % {"tests": os.path.join(ROOT, "tests"), "sim": sim, "road": road, "module": module}],
                            env=env, cwd=ROOT, capture_output=True, text=True, timeout=limit)
     except subprocess.TimeoutExpired:
         _ABNORMAL.append(road + ": time limit")
@@ -612,7 +613,7 @@ def check_in_child(sim, road, lib=None, limit=600):
     if r.returncode < 0 or r.returncode in (134, 137, 139):
         _ABNORMAL.append("%s: exit status %d" % (road, r.returncode))
     assert r.returncode >= 0, "the child was ended by signal %d\n%s" % (-r.returncode, r.stderr[-4000:])
-    assert r.returncode == 0 and "scope limits: ok" in r.stdout, r.stdout[-2000:] + r.stderr[-6000:]
+    assert r.returncode == 0 and module + ": ok" in r.stdout, r.stdout[-2000:] + r.stderr[-6000:]
 
 
 # ---- CPU tier: the conditions the generators must meet
