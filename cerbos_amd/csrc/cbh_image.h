@@ -68,7 +68,8 @@ static inline const char* cbh_parse_image(TableDev& d, std::vector<uint32_t>& me
   d.str_wflags = dptr(CBH_SEC_STR_WFLAGS);
   if (!d.str_wflags) return ("blob is missing the string flag section");
   if (d.inline_cols > CBH_CACHE_COLS || d.inline_cols > m[CBH_M_NCOLUMNS]) return ("blob inline column count out of range");
-  if (d.gslots_generic > d.gslots_all || d.gslots_all > CBH_W2_MAX_GSLOTS) return ("blob evaluation-site slots out of range");
+  // (the slot counts are cbh_walk2_kernel's: a table the lowering left to the general walk - more sites than slots among the reasons - files none)
+  if (d.gslots_generic > d.gslots_all || ((m[CBH_M_FLAGS] & CBH_MF_WALK2) && d.gslots_all > CBH_W2_MAX_GSLOTS)) return ("blob evaluation-site slots out of range");
   if (m[CBH_M_NROWS] && !d.rowpat) return ("blob is missing the row pattern section");
   d.rprows = (const u32*)dptr(CBH_SEC_RPROWS); d.n_rprows = m[CBH_M_NRPROWS];
   d.pool = (const u32*)dptr(CBH_SEC_U32POOL);
